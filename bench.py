@@ -1,6 +1,14 @@
 """bench.py — LEAD-YOLO hot path on MI355X.  Contract: see the task statement / DESIGN.md §6.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--scale s] [--size 640] [--dtype bf16|f32] [--mode train|forward]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times exactly K steps, and prints the line (`ms_per_step` = one timed step).  `--full` adds
+everything else the line can carry: 3 timed regions (median), the sustained run, the eager step, the per-kernel roofline probe, the step's
+kernel families, the pconv_rfcbam probes, the secondary forward figures and the CPU baseline.  `--dump-outputs DIR` writes what the timed
+path computed in its last timed step as DIR/<name>.npy (float32; a fixed seeded sample where the total would exceed 64 MB): train mode the
+loss, the loss items and the model's and the EMA's floating-point state after the step, forward mode the detections and the three levels'
+raw maps.  Inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 
 Default line = BASELINE.json's metric: images/sec (640x640) fwd+bwd — one "step" is one full optimisation step of
 lead-yolo-s at bs=64/GPU (BASELINE.json configs[2]): uint8 batch already resident in HBM -> train-mode forward ->
@@ -523,6 +531,36 @@ def print_layers(rows):
               f"{r.get('valu_flops', 0.0) / r['ms_per_launch'] / 1e9:7.2f} VALU TFLOP/s", file=sys.stderr)
 
 
+DUMP_MAX_BYTES = 64_000_000          # everything --dump-outputs writes, .npy headers included
+NPY_HEADER_BYTES = 1024              # per file: np.save writes 128 bytes of header for these shapes
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """arrays: name -> tensor.  Writes out_dir/<name>.npy in float32, at most `max_bytes` on disk in all.  Where the data would not fit,
+    every array gets a share of the budget proportional to its size and keeps that many elements of its flattened form at sorted positions
+    drawn from a generator seeded by the array's size (the same positions for the same shapes from run to run and build to build)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values()) * 4
+    budget = max_bytes - NPY_HEADER_BYTES * len(arrays)
+    for name, t in arrays.items():
+        t = t.detach().float().cpu()
+        if total > budget:
+            keep = max(1, int(t.numel() * budget // total))
+            if keep < t.numel():
+                idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(t.numel()))[:keep].sort()[0]
+                t = t.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+
+
+def train_outputs(model, ema, loss, items):
+    """what one optimisation step hands its caller: the loss and loss items it returns and the state it leaves behind (every floating-point
+    entry of the model's and the EMA's state dicts, concatenated in state-dict order)"""
+    def flat(sd):
+        return torch.cat([v.detach().float().reshape(-1) for v in sd.values() if v.is_floating_point()])
+    return {"loss": loss.reshape(-1), "loss_items": items.reshape(-1), "model_state": flat(model.state_dict()), "ema_state": flat(ema.ema.state_dict())}
+
+
 class Ctx:
     pass
 
@@ -585,7 +623,7 @@ def run_train(args, ctx):
     state = {}
 
     def eager_step():
-        state["loss"], _ = L.train_step(model, loss_fn, opt, imgs, tg, ema=ema, reducer=reducer, world_size=ctx.world, amp=amp)
+        state["loss"], state["items"] = L.train_step(model, loss_fn, opt, imgs, tg, ema=ema, reducer=reducer, world_size=ctx.world, amp=amp)
 
     step, launch = eager_step, "eager launches"
     if not args.no_graph:
@@ -597,7 +635,7 @@ def run_train(args, ctx):
                                    dp_exchange=args.dp_exchange)
 
             def step():
-                state["loss"], _ = g()
+                state["loss"], state["items"] = g()
             if ctx.world == 1:
                 launch = "hipGraph replay of the whole optimisation step"
             elif getattr(g, "_serial", False):
@@ -617,12 +655,14 @@ def run_train(args, ctx):
             step = eager_step
 
     regions = timed_repeats(ctx, step, args.steps, args.warmup, args.repeats)
-    sustained = sustained_run(ctx, step, statistics.median(regions) / args.steps) if not args.no_sustained else None
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, train_outputs(model, ema, state["loss"], state["items"]))
+    sustained = sustained_run(ctx, step, statistics.median(regions) / args.steps) if args.full and not args.no_sustained else None
     # The drop-in route (`python -m lead_yolo_amd.run train.py`) runs EAGER launches — one ctypes call per kernel from the
     # reference's unchanged Python loop: the same optimisation step without the hipGraph, so that the line says what that route costs
     # (not `value`: the contract's figure is the replayed step above).  Every rank runs it (at N > 1 the eager step exchanges gradients).
     eager_ms = None
-    if step is not eager_step:
+    if args.full and step is not eager_step:
         eager_ms = round(statistics.median(timed_repeats(ctx, eager_step, 5, 2, 2)) / 5 * 1e3, 4)
     res = dict(regions=regions, eager_ms_per_step=eager_ms, sustained=sustained, final_loss=float(state["loss"]), peak_mem_gib=round(torch.cuda.max_memory_allocated() / 2**30, 2), model=model, step=eager_step, launch=launch,
                workload=f"lead-yolo-{args.scale} bs={args.batch}/gpu 3x{args.size}x{args.size} {args.dtype} full train step: uint8 batch -> "
@@ -637,7 +677,7 @@ def run_train(args, ctx):
         res["rccl_ranks"] = ctx.dist.get_world_size()
         res["grad_buckets"] = len(reducer.buckets)
         res["grad_bytes"] = sum(b["flat"].numel() * b["flat"].element_size() for b in reducer.buckets)
-        if step is not eager_step:
+        if args.full and step is not eager_step:
             # where in the replayed backward every bucket's all-reduce is released (this rank), and what the step costs beside the
             # forward + backward graph alone: the driver computes scaling from the per-N values, this says WHY a step is longer than N = 1's
             try:
@@ -681,8 +721,15 @@ def run_forward(args, ctx, batch=None, steps=None, warmup=None, repeats=None):
             step, launch = g, "hipGraph replay"
         except Exception as e:                                  # noqa: BLE001
             print(f"[bench] hipGraph capture unavailable ({type(e).__name__}: {e}); timing eager launches", file=sys.stderr)
+    last = {}
+
+    def timed():
+        last["out"] = step()
     with torch.no_grad():
-        regions = timed_repeats(ctx, step, steps or args.steps, args.warmup if warmup is None else warmup, repeats or args.repeats)
+        regions = timed_repeats(ctx, timed, steps or args.steps, args.warmup if warmup is None else warmup, repeats or args.repeats)
+    if args.dump_outputs and ctx.rank == 0:
+        z, feats = last["out"]
+        dump_outputs(args.dump_outputs, {"pred": z, **{f"feat{i}": f for i, f in enumerate(feats)}})
     return dict(regions=regions, model=model, x=x, launch=launch, batch=batch,
                 step=lambda: model(x),
                 workload=f"lead-yolo-{args.scale} bs={batch}/gpu 3x{args.size}x{args.size} {args.dtype} eval forward (BASELINE.json configs[1]" + ("" if args.dtype == "f32" else " shape in bf16") + "); "
@@ -707,7 +754,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of --steps steps each; the line reports their median")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of --steps steps each; the line reports their median (default 1, 3 with --full)")
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default 64 for train, 32 for forward)")
     ap.add_argument("--scale", default="s")
     ap.add_argument("--size", type=int, default=640)
@@ -724,7 +771,16 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="time eager launches instead of replaying the captured hipGraph of the step")
     ap.add_argument("--dp-exchange", default="probe", choices=("probe", "serial", "overlapped"),
                     help="N > 1: gradient exchange form of the captured step (probe = time both at construction over the real group, keep the faster)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every secondary measurement and check: median of 3 timed regions, sustained run, eager step, per-kernel roofline probe, "
+                         "step families, pconv_rfcbam probes, secondary forward figures, CPU baseline (the --no-* options switch single ones off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if args.layers and not args.full:
+        ap.error("--layers prints the per-kernel table of the roofline probe, which only runs with --full")
     if args.train:
         args.mode = "train"
     if args.batch is None:
@@ -778,7 +834,7 @@ def main():
     # The per-kernel probe replays the EAGER step, which at N > 1 exchanges gradient buckets: every rank must run it (a rank-0-only probe
     # would pair its all-reduces with the other ranks' final barrier).  The table itself is only used on rank 0.
     rows = step_roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         if args.mode == "train":
             rows = probe_step(res["step"], iters=2)
             step_roof = step_roofline(args, ms_per_step, res["step"], rows)
@@ -806,7 +862,7 @@ def main():
         for k in ("final_loss", "peak_mem_gib", "rccl_ranks", "grad_buckets", "grad_bytes", "dp_overlap", "launch"):
             if k in res:
                 out[k if k != "launch" else "launch_mode"] = res[k]
-        if args.no_roofline:
+        if not args.full or args.no_roofline:
             out["roofline"] = None
             out["cpu_baseline"] = None
         else:
@@ -830,7 +886,7 @@ def main():
                     # secondary figure: the eval forward of configs[1] in ITS dtype (fp32), and the same shape in this line's dtype
                     out["forward"] = {}
                     for fdtype in dict.fromkeys(("f32", args.dtype)):
-                        fargs = argparse.Namespace(**{**vars(args), "dtype": fdtype})
+                        fargs = argparse.Namespace(**{**vars(args), "dtype": fdtype, "dump_outputs": None})
                         fw = run_forward(fargs, ctx, batch=32, steps=20, warmup=3, repeats=3)
                         fdt = statistics.median(fw["regions"])
                         out["forward"][fdtype] = {"metric": fw["metric"], "value": round(32 * 20 / fdt, 2), "unit": "images/sec", "ms_per_step": round(fdt / 20 * 1e3, 4),

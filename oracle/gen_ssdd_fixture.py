@@ -3,8 +3,9 @@ dataset LEAD-YOLO.yaml's nc = 1 recipe trains on, data/SSDD.yaml), letterboxed t
 side to the target, pad with 114; utils/augmentations.py `letterbox`) with their labels mapped into the letterboxed frame.  Data only:
 the images are single-channel SAR chips stored as (JPEG-noisy) RGB triples; their luma plane is kept, ONE uint8 plane each, and the tests
 feed it to all three input channels.
-tests/golden/ssdd_train48.npz (round 6): 48 images of the TRAIN split (data/SSDD/images/train), same format — what the accuracy test trains
-on, so that the 16 test-split images it scores are held out (data/SSDD.yaml: train and test are disjoint image sets).
+tests/golden/ssdd_train48_<i>.npz (round 6): 48 images of the TRAIN split (data/SSDD/images/train), same format, 16 per file (each file stays
+under 1 MiB; the labels carry the image's index among all 48) — what the accuracy test trains on, so that the 16 test-split images it scores
+are held out (data/SSDD.yaml: train and test are disjoint image sets).
     python oracle/gen_ssdd_fixture.py          (build container: /root/reference present)"""
 import glob
 import os
@@ -20,10 +21,10 @@ S, N = 320, 16
 
 def main():
     one("test", 16, "ssdd16.npz")
-    one("train", 48, "ssdd_train48.npz")
+    one("train", 48, "ssdd_train48_{}.npz", per_file=16)
 
 
-def one(split, N, name):
+def one(split, N, name, per_file=None):
     files = sorted(glob.glob(os.path.join(REF, "images", split, "*.jpg")))[:N]
     assert len(files) == N, f"SSDD {split} images not found (this script runs in the build container only)"
     imgs = np.full((N, S, S), 114, dtype=np.uint8)
@@ -45,9 +46,13 @@ def one(split, N, name):
                     targets.append([i, c, (x * nw + left) / S, (y * nh + top) / S, bw * nw / S, bh * nh / S])
         names.append(os.path.basename(f))
     targets = np.asarray(targets, dtype=np.float32).reshape(-1, 6)
-    out = os.path.join(ROOT, "tests", "golden", name)
-    np.savez_compressed(out, imgs=imgs, targets=targets, names=np.asarray(names))
-    print(f"{out}: {os.path.getsize(out) / 1024:.0f} KiB, {len(targets)} boxes in {N} images")
+    names = np.asarray(names)
+    per_file = per_file or N
+    for j, i0 in enumerate(range(0, N, per_file)):
+        sel = (targets[:, 0] >= i0) & (targets[:, 0] < i0 + per_file)
+        out = os.path.join(ROOT, "tests", "golden", name.format(j))
+        np.savez_compressed(out, imgs=imgs[i0:i0 + per_file], targets=targets[sel], names=names[i0:i0 + per_file])
+        print(f"{out}: {os.path.getsize(out) / 1024:.0f} KiB, {int(sel.sum())} boxes in {min(per_file, N - i0)} images")
 
 
 if __name__ == "__main__":

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +27,7 @@ def _run(extra, env=None, timeout=600):
 
 
 def test_single_gpu_line():
-    d = _run(["--steps", "3", "--warmup", "2", "--repeats", "1", "--batch", "8", "--no-cpu-baseline", "--no-secondary"])
+    d = _run(["--full", "--steps", "3", "--warmup", "2", "--repeats", "1", "--batch", "8", "--no-cpu-baseline", "--no-secondary"])
     assert KEYS <= set(d) and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 2 and d["dtype"] == "bf16" and d["scaling"] == "weak"
     assert d["metric"] == "images/sec (640x640) fwd+bwd" and d["value"] > 0 and d["higher_is_better"] is True and d["vs_baseline"] is None
     r = d["roofline"]
@@ -53,7 +54,7 @@ def test_single_gpu_line():
 
 @pytest.mark.parametrize("form", ["probe", "serial", "overlapped"])
 def test_two_rank_launch_path_dry_run(form):
-    d = _run(["--gpus", "2", "--steps", "2", "--warmup", "2", "--repeats", "1", "--batch", "4", "--no-cpu-baseline", "--dp-exchange", form],
+    d = _run(["--full", "--gpus", "2", "--steps", "2", "--warmup", "2", "--repeats", "1", "--batch", "4", "--no-cpu-baseline", "--dp-exchange", form],
              env={"LY_BENCH_ONE_GPU": "1", "LY_BENCH_BACKEND": "gloo"})
     pr = d["dp_overlap"].get("probe")
     assert pr and d["dp_overlap"]["rccl_ranks"] == 2, d["dp_overlap"]
@@ -74,3 +75,33 @@ def test_two_rank_launch_path_dry_run(form):
         assert "released mid-graph" in d["launch_mode"]
         assert len(ov["bucket_release_pct_of_graph_a"]) >= 1 and all(b["released_at_pct"] > 0 for b in ov["bucket_release_pct_of_graph_a"])
     assert abs(d["value"] - 2 * 4 * 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+
+
+@pytest.mark.parametrize("mode", ["train", "forward"])
+def test_plain_line_times_the_steps_and_dumps_outputs(mode, tmp_path):
+    """a plain run (no --full) times exactly --steps steps in one region, carries none of the secondary figures, and --dump-outputs writes
+    what the last timed step computed"""
+    b = 8 if mode == "train" else 4
+    d = _run(["--mode", mode, "--steps", "4", "--warmup", "2", "--batch", str(b), "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 4 and d["warmup"] == 2 and d["timed_repeats"] == 1 and len(d["repeat_ms_per_step"]) == 1
+    assert d["repeat_ms_per_step"][0] == d["ms_per_step"] and abs(d["value"] - b * 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and not {"sustained", "eager_ms_per_step", "forward"} & set(d)
+    got = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(p.stat().st_size for p in tmp_path.glob("*.npy")) <= 64_000_000
+    if mode == "train":
+        assert set(got) == {"loss", "loss_items", "model_state", "ema_state"}
+        assert float(got["loss"][0]) == d["final_loss"] and got["loss_items"].shape == (3,)
+        assert got["model_state"].shape == got["ema_state"].shape and got["model_state"].size > 3_000_000
+    else:
+        assert set(got) == {"pred", "feat0", "feat1", "feat2"}
+        # the dump is the eval forward of the benchmark's seeded model on its seeded batch: recomputed here, eagerly, in this process
+        import bench
+        import torch
+        dev = torch.device("cuda", 0)
+        with torch.no_grad():
+            z, feats = bench.build_model("s", dev)(bench.synth_batch(b, 640, 0, dev))
+        for name, ref in (("pred", z), *((f"feat{i}", f) for i, f in enumerate(feats))):
+            ref = ref.float().cpu().numpy()
+            assert got[name].shape == ref.shape, name
+            assert np.abs(got[name] - ref).max() <= 1e-4 * max(1.0, float(np.abs(ref).max())), name

@@ -121,12 +121,19 @@ def _stats_of(boxes_per_image, tg, size):
     return out
 
 
-TRAIN_FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ssdd_train48.npz")
+TRAIN_FIX = [os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", f"ssdd_train48_{i}.npz") for i in range(3)]
+
+
+def _train_fixture():
+    """the 48 TRAIN-split images, stored as three files of 16 (tests/golden/ssdd_train48_<i>.npz, oracle/gen_ssdd_fixture.py; the labels
+    carry the image's index among all 48)"""
+    parts = [np.load(f) for f in TRAIN_FIX]
+    return {k: np.concatenate([d[k] for d in parts]) for k in ("imgs", "targets", "names")}
 
 
 def _train_batches():
-    """the 48 TRAIN-split images (tests/golden/ssdd_train48.npz, oracle/gen_ssdd_fixture.py) as three batches of 16 with batch-local image indices"""
-    d = np.load(TRAIN_FIX)
+    """the 48 TRAIN-split images as three batches of 16 with batch-local image indices"""
+    d = _train_fixture()
     g = torch.from_numpy(d["imgs"]).unsqueeze(1).expand(-1, 3, -1, -1).contiguous()
     tg = torch.from_numpy(d["targets"])
     out = []
@@ -138,7 +145,7 @@ def _train_batches():
 
 
 def test_train_and_test_fixtures_are_disjoint_splits():
-    a, b = np.load(TRAIN_FIX), np.load(FIX)
+    a, b = _train_fixture(), np.load(FIX)
     assert a["imgs"].shape == (48, 320, 320) and not (set(a["names"].tolist()) & set(b["names"].tolist()))
 
 

@@ -10,7 +10,7 @@ cd $R
 timeout 1500 python -m pytest tests -m gpu -q ${PYTEST_ARGS:--x} ${K:+-k "$K"} > $OUT/${TAG}_pytest.log 2>&1
 echo "pytest rc=$?" >> $OUT/${TAG}_pytest.log
 tail -5 $OUT/${TAG}_pytest.log
-timeout 900 python bench.py --layers "$@" > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_kernels.txt
+timeout 900 python bench.py --full --layers "$@" > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_kernels.txt
 echo "bench rc=$?"
 tail -c 3000 $OUT/${TAG}_bench.json
 cd /tmp && export TMPDIR=/tmp
