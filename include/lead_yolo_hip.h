@@ -19,7 +19,7 @@ extern "C" {
 #endif
 
 enum { LY_F32 = 0, LY_BF16 = 1 };
-int ly_abi_version(void);      /* 2: dtype-polymorphic entry points */
+int ly_abi_version(void);      /* 3: ly_adam_step (2: dtype-polymorphic entry points) */
 const char* ly_last_error(void);
 
 /* FasterNet MLPBlock forward, eval form (BN folded to scale/shift):
@@ -613,6 +613,28 @@ typedef struct LyOptTensor {
  * 1 float receiving the pre-clip global gradient norm (what clip_grad_norm_ returns).                                              */
 int ly_optim_step(const LyOptTensor* table, const int* blk_tensor, const long* blk_off, int n_blocks, double* ws, float* hyper,
                   float* norm_out, void* stream);
+
+/* ---- fused Adam / AdamW step (reference utils/torch_utils.py:318-346 smart_optimizer "Adam" / "AdamW"; torch.optim.Adam foreach
+ * update) — the same table form as ly_optim_step: clip + Adam or AdamW + zero_grad (+ EMA) per entry, EMA only where g == NULL.      */
+typedef struct LyAdamTensor {
+  float* p;            /* parameter (or buffer) */
+  float* g;            /* gradient, zeroed after use; NULL = no optimiser update */
+  float* m;            /* exp_avg (same size and layout as p); unused when g == NULL */
+  float* v;            /* exp_avg_sq (same size and layout as p); unused when g == NULL */
+  float* ema;          /* EMA copy of p, or NULL */
+  long n;              /* elements */
+  float wd;            /* weight decay of the tensor's group */
+  int group;           /* index of its learning rate in hyper[0..2] */
+  int taps, cin;       /* taps > 1: g is stored tap-major [cout][taps][cin] while p is [cout][cin][taps] (k x k conv weights) */
+  int step0;           /* the entry's Adam step this call is t = T + 1 - step0 (T = hyper[11]; t >= 1) */
+} LyAdamTensor;
+/* table / blk_tensor / blk_off / ws / norm_out as for ly_optim_step.  hyper (device, 12 floats): lr[3], beta1, beta2, eps, max_norm
+ * (<= 0: none), ema decay (< 0: none), ema tau, ema updates so far, gradient scale, T = optimiser steps so far (an integer; the call
+ * increments hyper[9] and hyper[11]).  decoupled != 0: AdamW (p *= 1 - lr*wd before the update), 0: Adam (g += wd*p after clipping).
+ * Per element, t = T + 1 - step0, bias corrections 1 - beta^t in double:
+ *   m = lerp(m, g, 1 - beta1);  v = beta2*v + (1 - beta2)*g*g;  p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)   */
+int ly_adam_step(const LyAdamTensor* table, const int* blk_tensor, const long* blk_off, int n_blocks, double* ws, float* hyper,
+                 int decoupled, float* norm_out, void* stream);
 
 /* ---- events across a hipGraph boundary (data-parallel step; replaces what DistributedDataParallel's reducer does with autograd hooks and
  * side streams, reference utils/torch_utils.py:55-63, train.py:233-235) ----------------------------------------------------------

@@ -63,6 +63,11 @@ class LyOptTensor(ctypes.Structure):
     _fields_ = [("p", _P), ("g", _P), ("buf", _P), ("ema", _P), ("n", _L), ("wd", _F), ("group", _I), ("taps", _I), ("cin", _I)]
 
 
+class LyAdamTensor(ctypes.Structure):
+    _fields_ = [("p", _P), ("g", _P), ("m", _P), ("v", _P), ("ema", _P), ("n", _L), ("wd", _F), ("group", _I), ("taps", _I), ("cin", _I),
+                ("step0", _I)]
+
+
 class LyPackDesc(ctypes.Structure):
     _fields_ = [("src", _P), ("dst", _P), ("r_valid", _I), ("K", _I), ("planes", _I), ("S", _I), ("t0", _I), ("T", _I),
                 ("nrb", _I), ("nb", _I), ("nc", _I), ("vb", _I), ("vc", _I),
@@ -171,6 +176,7 @@ SIGNATURES = {
     "ly_f64_add": [ctypes.POINTER(LyF64AddTable), _P],
     "ly_pack_table": [_P, _P, _I, _P],
     "ly_optim_step": [_P, _P, _P, _I, _P, _P, _P, _P],
+    "ly_adam_step": [_P, _P, _P, _I, _P, _P, _I, _P, _P],
     "ly_sum_rows": [_P, _L, _L, _L, _P, _I, _P],
     "ly_sum_rows_f64": [_P, _I, _I, _P, _P],
     "ly_rf1_bwd": [ctypes.POINTER(LyRf1BwdParams), _I, _P],

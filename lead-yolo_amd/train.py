@@ -1,12 +1,13 @@
 """The reference's optimisation step (train.py:295-341) on the HIP model: SURVEY.md §8 row T.
 
     imgs.float()/255 -> forward (train-mode, HIP) -> ComputeLoss -> backward (HIP, grad.py) ->
-    [gradient all-reduce, ddp.GradReducer] -> clip_grad_norm_(10) -> SGD(nesterov) -> [EMA]
+    [gradient all-reduce, ddp.GradReducer] -> clip_grad_norm_(10) -> SGD(nesterov) / Adam / AdamW -> [EMA]
 
 Mirrors `smart_optimizer` (utils/torch_utils.py:318-346: three parameter groups — biases without decay,
 BatchNorm weights without decay, all other weights with decay) and `ModelEMA` (utils/torch_utils.py:404-432).
-The optimiser is optim.FusedSGD on the GPU (clip + SGD-nesterov + zero_grad + EMA for every tensor in three launches, csrc/ly_optim.hip);
-`smart_optimizer(..., fused=False)` returns the reference's torch.optim.SGD object.
+The optimiser is a fused optimiser on the GPU: optim.FusedSGD (clip + SGD-nesterov + zero_grad + EMA for every tensor in three launches,
+csrc/ly_optim.hip) or optim.FusedAdam / FusedAdamW (csrc/ly_adam.hip); `smart_optimizer(..., fused=False)` returns the reference's
+torch.optim object.
 """
 import ctypes
 import math
@@ -36,19 +37,33 @@ def param_groups(model):
 
 
 def smart_optimizer(model, name="SGD", lr=0.001, momentum=0.9, decay=1e-5, fused=None, max_norm=10.0):
-    """The reference's three groups (utils/torch_utils.py:318-346).  fused=True (default when the parameters live on the GPU):
-    optim.FusedSGD — clip + SGD-nesterov + zero_grad (+ EMA) in two launches; fused=False: torch.optim.SGD, exactly the
-    reference's object."""
+    """The reference's optimiser and three groups (utils/torch_utils.py:318-346): name in SGD (nesterov), Adam, AdamW (betas =
+    (momentum, 0.999), AdamW's own decay 0.0), RMSProp.  fused=True (default when the parameters live on the GPU): the fused
+    optimiser — optim.FusedSGD / FusedAdam / FusedAdamW, clip + update + zero_grad (+ EMA) in a few launches; fused=False: the
+    torch.optim object, exactly the reference's.  RMSProp has no fused form: it needs fused=False."""
     bias, dec, norm = param_groups(model)
-    if name != "SGD":
-        raise NotImplementedError("the LEAD-YOLO recipe trains with SGD(nesterov); other optimisers are not wired")
+    if name not in ("SGD", "Adam", "AdamW", "RMSProp"):
+        raise NotImplementedError(f"Optimizer {name} not implemented.")
     if fused is None:
         fused = all(p.is_cuda for p in bias + dec + norm)
     if fused:
-        from .optim import FusedSGD
-        opt = FusedSGD(bias, lr=lr, momentum=momentum, nesterov=True, max_norm=max_norm)
-    else:
+        from . import optim
+        if name == "SGD":
+            opt = optim.FusedSGD(bias, lr=lr, momentum=momentum, nesterov=True, max_norm=max_norm)
+        elif name == "Adam":
+            opt = optim.FusedAdam(bias, lr=lr, betas=(momentum, 0.999), max_norm=max_norm)
+        elif name == "AdamW":
+            opt = optim.FusedAdamW(bias, lr=lr, betas=(momentum, 0.999), weight_decay=0.0, max_norm=max_norm)
+        else:
+            raise NotImplementedError("RMSProp has no fused optimiser: smart_optimizer(..., 'RMSProp', fused=False) gives torch.optim.RMSprop")
+    elif name == "SGD":
         opt = torch.optim.SGD(bias, lr=lr, momentum=momentum, nesterov=True)
+    elif name == "Adam":
+        opt = torch.optim.Adam(bias, lr=lr, betas=(momentum, 0.999))
+    elif name == "AdamW":
+        opt = torch.optim.AdamW(bias, lr=lr, betas=(momentum, 0.999), weight_decay=0.0)
+    else:
+        opt = torch.optim.RMSprop(bias, lr=lr, momentum=momentum)
     opt.add_param_group({"params": dec, "weight_decay": decay})
     opt.add_param_group({"params": norm, "weight_decay": 0.0})
     return opt
@@ -93,7 +108,8 @@ def forward_backward(model, compute_loss, imgs, targets, world_size=1, amp=None)
 
 
 def optimizer_step(model, optimizer, ema=None, max_norm=10.0, reducer=None):
-    """clip + SGD-nesterov + zero_grad (+ EMA): two launches with optim.FusedSGD, the reference's torch calls otherwise"""
+    """clip + update + zero_grad (+ EMA): a few launches with a fused optimiser (optim.FusedSGD / FusedAdam / FusedAdamW), the reference's
+    torch calls otherwise"""
     if getattr(optimizer, "fused", False):
         if ema is not None and (optimizer._ema is None or optimizer._ema[0] is not ema):
             optimizer.attach_ema(ema, model)
@@ -110,11 +126,11 @@ def optimizer_step(model, optimizer, ema=None, max_norm=10.0, reducer=None):
 
 
 def _set_deferred_average(optimizer, reducer):
-    """with the fused optimiser the mean over ranks costs nothing: buckets are all-reduced as SUMs and FusedSGD reads every gradient as
+    """with a fused optimiser the mean over ranks costs nothing: buckets are all-reduced as SUMs and the optimiser reads every gradient as
     g / world (one device scalar) — instead of one division launch per bucket.
     Every step re-derives both flags from the pair it is given, so neither sticks: an optimiser later used WITHOUT the reducer reads plain
     gradients again, and a reducer later paired with a non-fused optimiser (torch.optim.SGD, gradient logging, clip_grad_norm_) goes back
-    to averaging its buckets itself — `p.grad` is the SUM over ranks only while a FusedSGD with grad_scale = 1 / world is the consumer."""
+    to averaging its buckets itself — `p.grad` is the SUM over ranks only while a fused optimiser with grad_scale = 1 / world is the consumer."""
     fused = getattr(optimizer, "fused", False)
     if reducer is None:
         if fused and optimizer.grad_scale != 1.0:
@@ -158,10 +174,10 @@ DP_MARK_EVERY = 1                 # development: an event node only at every k-t
 
 
 class GraphedTrainStep:
-    """The whole optimisation step — uint8 batch -> forward -> loss -> backward -> clip + SGD-nesterov + zero_grad (+ EMA) — captured
+    """The whole optimisation step — uint8 batch -> forward -> loss -> backward -> clip + fused update + zero_grad (+ EMA) — captured
     once into hipGraphs and replayed with no per-launch host work.  Possible because every C-ABI entry point only
-    launches on the current stream, the device loss has no host sync, and optim.FusedSGD keeps its step-dependent scalars (learning
-    rates, EMA ramp, step counter, gradient scale) in device memory.
+    launches on the current stream, the device loss has no host sync, and the fused optimisers (optim.FusedSGD / FusedAdam / FusedAdamW)
+    keep their step-dependent scalars (learning rates, EMA ramp, step counters, gradient scale) in device memory.
 
         step = GraphedTrainStep(model, compute_loss, optimizer, imgs, targets, ema=ema, amp=torch.bfloat16)
         loss, items = step(next_imgs, next_targets)        # same shapes / dtypes; pad `targets` with rows whose image index is -1
@@ -178,7 +194,7 @@ class GraphedTrainStep:
     bucket's completion point is an event-record node (csrc ly_event_record); right after launching A the host queues, per bucket in
     completion order, `wait for its event` + `all_reduce(bucket)` on a communication stream, so RCCL starts on a bucket while the graph
     is still executing the rest of the backward; graph B = the fused optimiser (which also divides by the world size:
-    FusedSGD.grad_scale — no division pass per bucket) runs when the last exchange is done.  The ~10 all-reduce launches are the only
+    the optimiser's grad_scale — no division pass per bucket) runs when the last exchange is done.  The ~10 all-reduce launches are the only
     eager work of a step.  Serial: graph A -> one all-reduce of the reducer's master buffer issued from the step's stream -> graph B.
 
     accumulate = k (the reference's gradient accumulation, train.py:157,300,330): call k times with k micro-batches; graph A runs every
@@ -187,7 +203,7 @@ class GraphedTrainStep:
     def __init__(self, model, compute_loss, optimizer, imgs, targets, ema=None, amp=None, max_norm=10.0, warmup=3, reducer=None, world_size=1,
                  accumulate=1, dp_exchange=None):
         if not getattr(optimizer, "fused", False):
-            raise NotImplementedError("GraphedTrainStep needs optim.FusedSGD (smart_optimizer(..., fused=True)): torch.optim.SGD + "
+            raise NotImplementedError("GraphedTrainStep needs a fused optimiser (smart_optimizer(..., fused=True)): the torch.optim objects + "
                                       "clip_grad_norm_ keep per-step host state")
         from . import capi, pack
         self.imgs, self.targets = imgs.clone(), targets.clone()
@@ -282,16 +298,12 @@ class GraphedTrainStep:
 
     # ---- which exchange form: measured, at the actual world size -----------------------------------------------------------------
     def _dp_state(self):
-        """every tensor an optimisation step changes (parameters, BatchNorm buffers, momentum, EMA, the optimiser's device scalars): the probe
-        replays real steps and puts them back"""
+        """every tensor an optimisation step changes (parameters, BatchNorm buffers, EMA, the optimiser's state tensors — momentum or Adam
+        moments — and device scalars, the Adam step counter among them): the probe replays real steps and puts them back"""
         ts = [v for v in self.model.state_dict().values()]
-        ts += [st["momentum_buffer"] for g in self.optimizer.param_groups for p in g["params"]
-               for st in (self.optimizer.state.get(p, {}),) if st.get("momentum_buffer") is not None]
         if self.ema is not None:
             ts += list(self.ema.ema.state_dict().values())
-        t = self.optimizer._table
-        ts += [t["hyper"], t["ws"], self.optimizer.grad_norm]
-        return ts
+        return ts + self.optimizer.device_state()
 
     def _choose_exchange(self):
         import torch.distributed as dist
