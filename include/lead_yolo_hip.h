@@ -291,6 +291,29 @@ int ly_detect_tail(const void* y /*T*/, int ldy, int n_img, int H, int W, int na
 int ly_detect_level(const void* x /*T*/, int ldx, int n_img, int H, int W, int K, const void* wp, int nat, const float* bias, int na, int no,
                     const float* anchors, float stride, float* p, float* z, long zrows, long zoff, int dtype, void* stream);
 int ly_detect_level_ok(int K, int na, int no, int dtype);     /* 1 when ly_detect_level is built for this shape */
+/* Test-time augmentation (models/yolo.py DetectionModel._forward_augment / _descale_pred): ly_detect_level / ly_detect_tail with the decoded rows
+ * descaled before the store — z[..., :4] / dscale (a true division), then z[..., 0] = img_w - z[..., 0] when dflip != 0 (the left-right flipped
+ * pass; img_w = the un-augmented image width).  p may be NULL (augmented inference returns no raw maps); z is required.                  */
+int ly_detect_level_aug(const void* x /*T*/, int ldx, int n_img, int H, int W, int K, const void* wp, int nat, const float* bias, int na, int no,
+                        const float* anchors, float stride, float* p, float* z, long zrows, long zoff, float dscale, int dflip, float img_w,
+                        int dtype, void* stream);
+int ly_detect_tail_aug(const void* y /*T*/, int ldy, int n_img, int H, int W, int na, int no, const float* anchors, float stride,
+                       float* p, float* z, long zrows, long zoff, float dscale, int dflip, float img_w, int dtype, void* stream);
+
+/* Image resampling of test-time augmentation (utils/torch_utils.py scale_img, same_shape=False, csrc/ly_augment.hip).  One launch writes up to
+ * LY_SCALE_IMG_MAX outputs of one NCHW image batch x[n_img, C, H, W]: for each spec, the (optionally left-right flipped) image resized to
+ * Hs x Ws with F.interpolate(mode='bilinear', align_corners=False) arithmetic, in the top-left corner of an Ho x Wo canvas whose remaining
+ * pixels hold `pad` (F.pad(value=0.447)).  Element type: dtype LY_F32, LY_BF16 or LY_F16 (input and outputs alike); fp32 arithmetic, one
+ * rounding.  Wo must be a multiple of 16 / sizeof(element), out 16-byte aligned.                                                            */
+enum { LY_F16 = 2 };            /* fp16 storage: accepted by ly_scale_img only (the model computes an fp16 batch as bf16, ops.edge_in) */
+#define LY_SCALE_IMG_MAX 4
+typedef struct LyScaleImgSpec {
+  void* out;              /* [n_img, C, Ho, Wo] (T)                                                   */
+  int Hs, Ws;             /* resized size, 1 <= Hs <= Ho, 1 <= Ws <= Wo                                */
+  int Ho, Wo;             /* padded size                                                              */
+  int flip;               /* != 0: resample x.flip(3)                                                 */
+} LyScaleImgSpec;
+int ly_scale_img(const void* x /*T*/, int n_img, int C, int H, int W, const LyScaleImgSpec* specs, int nspec, float pad, int dtype, void* stream);
 /* Adjoint of that permute for the training step (models/yolo.py:88): dp fp32 [n, na, H, W, no] -> du rows [n*H*W][ldu] of T (column a*no+o;
  * columns >= na*no written as zero: the operand of the head's dgrad / wgrad), dbias[a*no+o] += sum over pixels.  W <= 160, na*no <= ldu <= 32. */
 int ly_detect_head_bwd(const float* dp, int n_img, int H, int W, int na, int no, void* du /*T*/, int ldu, float* dbias,

@@ -68,6 +68,13 @@ class LyAdamTensor(ctypes.Structure):
                 ("step0", _I)]
 
 
+SCALE_IMG_MAX = 4                          # LY_SCALE_IMG_MAX
+
+
+class LyScaleImgSpec(ctypes.Structure):
+    _fields_ = [("out", _P), ("Hs", _I), ("Ws", _I), ("Ho", _I), ("Wo", _I), ("flip", _I)]
+
+
 class LyPackDesc(ctypes.Structure):
     _fields_ = [("src", _P), ("dst", _P), ("r_valid", _I), ("K", _I), ("planes", _I), ("S", _I), ("t0", _I), ("T", _I),
                 ("nrb", _I), ("nb", _I), ("nc", _I), ("vb", _I), ("vc", _I),
@@ -83,6 +90,7 @@ class LyWgradParams(ctypes.Structure):
 
 STATS_STRIPES = 32
 LY_F32, LY_BF16 = 0, 1                     # `dtype` codes of the C ABI
+LY_F16 = 2                                 # fp16 storage: ly_scale_img only
 
 
 def dtype_code(t):
@@ -172,6 +180,9 @@ SIGNATURES = {
     "ly_detect_tail": [_P, _I, _I, _I, _I, _I, _I, _P, _F, _P, _P, _L, _L, _I, _P],
     "ly_detect_level": [_P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _F, _P, _P, _L, _L, _I, _P],
     "ly_detect_level_ok": [_I, _I, _I, _I],
+    "ly_detect_tail_aug": [_P, _I, _I, _I, _I, _I, _I, _P, _F, _P, _P, _L, _L, _F, _I, _F, _I, _P],
+    "ly_detect_level_aug": [_P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _F, _P, _P, _L, _L, _F, _I, _F, _I, _P],
+    "ly_scale_img": [_P, _I, _I, _I, _I, ctypes.POINTER(LyScaleImgSpec), _I, _F, _I, _P],
     "ly_detect_head_bwd": [_P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P],
     "ly_f64_add": [ctypes.POINTER(LyF64AddTable), _P],
     "ly_pack_table": [_P, _P, _I, _P],

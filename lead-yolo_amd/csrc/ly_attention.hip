@@ -891,10 +891,12 @@ extern "C" int ly_sppf_pool(const void* x, int ldx, int n_img, int H, int W, int
 // ldy) write the raw map p[n, a, h, w, o] and, in eval mode, the decoded rows z[n, zoff + (a*H + h)*W + w, o]:
 //   xy = (2*sig - 0.5 + grid) * stride,  wh = (2*sig)^2 * anchor*stride,  rest = sig.
 // ---------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(LY_THREADS) void ly_detect_tail_kernel(const T* __restrict__ y, int ldy, long total, int H, int W, int na, int no,
-                                                                    const float* __restrict__ anchors /* [na,2] grid units */, float stride,
-                                                                    float* __restrict__ p, float* __restrict__ z, long zrows, long zoff) {
+// AUG: the _descale_pred step of test-time augmentation on the decoded rows (see ly_detect_level_body in ly_detect.hip); p may be NULL there.
+template <typename T, bool AUG>
+__device__ __forceinline__ void ly_detect_tail_body(const T* __restrict__ y, int ldy, long total, int H, int W, int na, int no,
+                                                    const float* __restrict__ anchors /* [na,2] grid units */, float stride,
+                                                    float* __restrict__ p, float* __restrict__ z, long zrows, long zoff, float dscale, int dflip,
+                                                    float img_w) {
   const long i = (long)blockIdx.x * LY_THREADS + threadIdx.x;      // over n*na*H*W*no, output order
   if (i >= total) return;
   const int o = (int)(i % no);
@@ -904,15 +906,37 @@ __global__ __launch_bounds__(LY_THREADS) void ly_detect_tail_kernel(const T* __r
   const int a = (int)(t % na);
   const long n = t / na;
   const float v = ly_ld1<T>(y + ((n * H + h) * W + w) * ldy + a * no + o);
-  p[i] = v;
+  if constexpr (AUG) {
+    if (p) p[i] = v;
+  } else {
+    p[i] = v;
+  }
   if (z) {
     const float s = ly_sigmoid(v);
     float r = s;
     if (o == 0) r = (s * 2.f + ((float)w - 0.5f)) * stride;
     else if (o == 1) r = (s * 2.f + ((float)h - 0.5f)) * stride;
     else if (o == 2 || o == 3) { const float q = s * 2.f; r = q * q * (anchors[a * 2 + (o - 2)] * stride); }
+    if constexpr (AUG) {
+      if (o < 4) r = r / dscale;
+      if (o == 0 && dflip) r = img_w - r;
+    }
     z[(n * zrows + zoff + ((long)a * H + h) * W + w) * no + o] = r;
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(LY_THREADS) void ly_detect_tail_kernel(const T* __restrict__ y, int ldy, long total, int H, int W, int na, int no,
+                                                                    const float* __restrict__ anchors /* [na,2] grid units */, float stride,
+                                                                    float* __restrict__ p, float* __restrict__ z, long zrows, long zoff) {
+  ly_detect_tail_body<T, false>(y, ldy, total, H, W, na, no, anchors, stride, p, z, zrows, zoff, 1.f, 0, 0.f);
+}
+
+template <typename T>
+__global__ __launch_bounds__(LY_THREADS) void ly_detect_tail_aug_kernel(const T* __restrict__ y, int ldy, long total, int H, int W, int na, int no,
+                                                                        const float* __restrict__ anchors, float stride, float* __restrict__ p,
+                                                                        float* __restrict__ z, long zrows, long zoff, float dscale, int dflip, float img_w) {
+  ly_detect_tail_body<T, true>(y, ldy, total, H, W, na, no, anchors, stride, p, z, zrows, zoff, dscale, dflip, img_w);
 }
 
 extern "C" int ly_detect_tail(const void* y, int ldy, int n_img, int H, int W, int na, int no, const float* anchors, float stride,
@@ -922,6 +946,18 @@ extern "C" int ly_detect_tail(const void* y, int ldy, int n_img, int H, int W, i
   const long total = (long)n_img * na * H * W * no;
   LY_WITH_T(dtype, hipLaunchKernelGGL(ly_detect_tail_kernel<T>, dim3((unsigned)((total + LY_THREADS - 1) / LY_THREADS)), dim3(LY_THREADS), 0,
                                       reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const T*>(y), ldy, total, H, W, na, no, anchors, stride, p, z, zrows, zoff));
+  LY_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ly_detect_tail_aug(const void* y, int ldy, int n_img, int H, int W, int na, int no, const float* anchors, float stride,
+                                  float* p, float* z, long zrows, long zoff, float dscale, int dflip, float img_w, int dtype, void* stream) {
+  LY_CHECK_DTYPE(dtype, "detect_tail_aug");
+  LY_CHECK(y && z && anchors && dscale > 0.f, "detect_tail_aug: null pointer / bad descale");
+  const long total = (long)n_img * na * H * W * no;
+  LY_WITH_T(dtype, hipLaunchKernelGGL(ly_detect_tail_aug_kernel<T>, dim3((unsigned)((total + LY_THREADS - 1) / LY_THREADS)), dim3(LY_THREADS), 0,
+                                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const T*>(y), ldy, total, H, W, na, no, anchors, stride, p, z,
+                                      zrows, zoff, dscale, dflip, img_w));
   LY_LAUNCH_CHECK();
   return 0;
 }

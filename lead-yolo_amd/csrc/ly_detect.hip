@@ -11,12 +11,16 @@
 
 #define LY_DET_LD 36            // floats per pixel row of a wave's output tile in LDS (32 channels + pad, rows 16-byte aligned)
 
-template <typename T, int S, bool NAT>
+// AUG (test-time augmentation, ly_detect_level_aug): _descale_pred of models/yolo.py applied to the decoded rows before the store — xywh / dscale
+// (a true division, as torch's `/=`), then x = img_w - x for the left-right flipped pass; p may be NULL.  A compile-time flag: the plain
+// instantiations below are the kernels they were.
+template <typename T, int S, bool NAT, bool AUG>
 __global__ __launch_bounds__(LY_THREADS) void ly_detect_level_kernel(const T* __restrict__ x, const int ldx, const long M, const int H, const int W,
                                                                       const uint4* __restrict__ wp, const float* __restrict__ bias, const int na,
                                                                       const int no, const float* __restrict__ anchors, const float stride,
                                                                       float* __restrict__ p, float* __restrict__ z, const long zrows, const long zoff,
-                                                                      const int ntiles, const int tpw) {
+                                                                      const int ntiles, const int tpw, const float dscale, const int dflip,
+                                                                      const float img_w) {
   constexpr int PL = LyT<T>::PL;
   extern __shared__ uint4 ly_det_w[];                       // [2 tiles][S][PL][64 lanes]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -109,7 +113,11 @@ __global__ __launch_bounds__(LY_THREADS) void ly_detect_level_kernel(const T* __
       const int n = ly_fdiv((int)mm, HW, invHW);
       const int hw = (int)mm - n * HW;
       const float v = ot[pl * LY_DET_LD + a * no + o];
-      p[(((long)n * na + a) * HW + hw) * no + o] = v;
+      if constexpr (AUG) {
+        if (p) p[(((long)n * na + a) * HW + hw) * no + o] = v;
+      } else {
+        p[(((long)n * na + a) * HW + hw) * no + o] = v;
+      }
       if (z) {
         const int h = ly_fdiv(hw, W, invW);
         const int w = hw - h * W;
@@ -118,6 +126,10 @@ __global__ __launch_bounds__(LY_THREADS) void ly_detect_level_kernel(const T* __
         if (o == 0) r = (sg * 2.f + ((float)w - 0.5f)) * stride;
         else if (o == 1) r = (sg * 2.f + ((float)h - 0.5f)) * stride;
         else if (o == 2 || o == 3) { const float d = sg * 2.f; r = d * d * (anchors[a * 2 + (o - 2)] * stride); }
+        if constexpr (AUG) {
+          if (o < 4) r = r / dscale;
+          if (o == 0 && dflip) r = img_w - r;
+        }
         z[((long)n * zrows + zoff + (long)a * HW + hw) * no + o] = r;
       }
     }
@@ -125,9 +137,9 @@ __global__ __launch_bounds__(LY_THREADS) void ly_detect_level_kernel(const T* __
   }
 }
 
-template <typename T, int S>
+template <typename T, int S, bool AUG>
 static void detect_level_launch(const int nat, const void* x, int ldx, long M, int H, int W, const void* wp, const float* bias, int na, int no, const float* anchors,
-                                float stride, float* p, float* z, long zrows, long zoff, hipStream_t st) {
+                                float stride, float* p, float* z, long zrows, long zoff, float dscale, int dflip, float img_w, hipStream_t st) {
   const int ntiles = (int)((M + 15) / 16);
   // tiles per wave: one until every SIMD holds ~4 waves, then more (the 2 x K weight rows a block stages are amortised over 4 tpw tiles).
   // Measured at bs=16 (one round of blocks): every further tile per wave adds ~5 us — a tile is one serial chain of memory round trips.
@@ -137,33 +149,51 @@ static void detect_level_launch(const int nat, const void* x, int ldx, long M, i
   const size_t lds = (size_t)2 * S * LyT<T>::PL * 64 * sizeof(uint4) + (LY_THREADS / 64) * 16 * LY_DET_LD * sizeof(float);
   const dim3 grid((unsigned)((ntiles + per_block - 1) / per_block));
   if (nat)
-    hipLaunchKernelGGL((ly_detect_level_kernel<T, S, true>), grid, dim3(LY_THREADS), lds, st, reinterpret_cast<const T*>(x), ldx, M, H, W,
-                       reinterpret_cast<const uint4*>(wp), bias, na, no, anchors, stride, p, z, zrows, zoff, ntiles, tpw);
+    hipLaunchKernelGGL((ly_detect_level_kernel<T, S, true, AUG>), grid, dim3(LY_THREADS), lds, st, reinterpret_cast<const T*>(x), ldx, M, H, W,
+                       reinterpret_cast<const uint4*>(wp), bias, na, no, anchors, stride, p, z, zrows, zoff, ntiles, tpw, dscale, dflip, img_w);
   else
-    hipLaunchKernelGGL((ly_detect_level_kernel<T, S, false>), grid, dim3(LY_THREADS), lds, st, reinterpret_cast<const T*>(x), ldx, M, H, W,
-                       reinterpret_cast<const uint4*>(wp), bias, na, no, anchors, stride, p, z, zrows, zoff, ntiles, tpw);
+    hipLaunchKernelGGL((ly_detect_level_kernel<T, S, false, AUG>), grid, dim3(LY_THREADS), lds, st, reinterpret_cast<const T*>(x), ldx, M, H, W,
+                       reinterpret_cast<const uint4*>(wp), bias, na, no, anchors, stride, p, z, zrows, zoff, ntiles, tpw, dscale, dflip, img_w);
+}
+
+template <bool AUG>
+static int detect_level_entry(const char* who, const void* x, int ldx, int n_img, int H, int W, int K, const void* wp, int nat, const float* bias,
+                              int na, int no, const float* anchors, float stride, float* p, float* z, long zrows, long zoff, float dscale, int dflip,
+                              float img_w, int dtype, void* stream) {
+  LY_CHECK((dtype) == LY_F32 || (dtype) == LY_BF16, "%s: unknown dtype %d", who, dtype);
+  if constexpr (AUG)
+    LY_CHECK(x && wp && bias && anchors && z && n_img > 0 && H > 0 && W > 0 && dscale > 0.f, "%s: null pointer / bad sizes", who);
+  else
+    LY_CHECK(x && wp && bias && anchors && p && n_img > 0 && H > 0 && W > 0, "%s: null pointer / bad sizes", who);
+  LY_CHECK(na * no <= 32 && na > 0 && no > 0, "%s: na*no = %d exceeds the 32 output rows of the kernel", who, na * no);
+  const int vw = dtype == LY_BF16 ? 8 : 4;
+  LY_CHECK((K & 31) == 0 && ldx >= K && (ldx % vw) == 0 && ((uintptr_t)x & 15) == 0, "%s: K = %d must be a multiple of 32, rows 16-byte aligned", who, K);
+  const long M = (long)n_img * H * W;
+  LY_CHECK(M < (1L << 24), "%s: too many pixels", who);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int S = K / 32;
+#define LY_DET(S_) LY_WITH_T(dtype, (detect_level_launch<T, S_, AUG>(nat, x, ldx, M, H, W, wp, bias, na, no, anchors, stride, p, z, zrows, zoff, dscale, dflip, img_w, st)))
+  if (S == 2) LY_DET(2);
+  else if (S == 4) LY_DET(4);
+  else if (S == 8) LY_DET(8);
+  else if (S == 16 && dtype == LY_BF16) detect_level_launch<__bf16, 16, AUG>(nat, x, ldx, M, H, W, wp, bias, na, no, anchors, stride, p, z, zrows, zoff, dscale, dflip, img_w, st);
+  else { ly_set_error("%s: K = %d is not built (64, 128, 256; 512 in bf16)", who, K); return -1; }
+#undef LY_DET
+  LY_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int ly_detect_level(const void* x, int ldx, int n_img, int H, int W, int K, const void* wp, int nat, const float* bias, int na, int no,
                                const float* anchors, float stride, float* p, float* z, long zrows, long zoff, int dtype, void* stream) {
-  LY_CHECK_DTYPE(dtype, "detect_level");
-  LY_CHECK(x && wp && bias && anchors && p && n_img > 0 && H > 0 && W > 0, "detect_level: null pointer / bad sizes");
-  LY_CHECK(na * no <= 32 && na > 0 && no > 0, "detect_level: na*no = %d exceeds the 32 output rows of the kernel", na * no);
-  const int vw = dtype == LY_BF16 ? 8 : 4;
-  LY_CHECK((K & 31) == 0 && ldx >= K && (ldx % vw) == 0 && ((uintptr_t)x & 15) == 0, "detect_level: K = %d must be a multiple of 32, rows 16-byte aligned", K);
-  const long M = (long)n_img * H * W;
-  LY_CHECK(M < (1L << 24), "detect_level: too many pixels");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int S = K / 32;
-#define LY_DET(S_) LY_WITH_T(dtype, (detect_level_launch<T, S_>(nat, x, ldx, M, H, W, wp, bias, na, no, anchors, stride, p, z, zrows, zoff, st)))
-  if (S == 2) LY_DET(2);
-  else if (S == 4) LY_DET(4);
-  else if (S == 8) LY_DET(8);
-  else if (S == 16 && dtype == LY_BF16) detect_level_launch<__bf16, 16>(nat, x, ldx, M, H, W, wp, bias, na, no, anchors, stride, p, z, zrows, zoff, st);
-  else { ly_set_error("detect_level: K = %d is not built (64, 128, 256; 512 in bf16)", K); return -1; }
-#undef LY_DET
-  LY_LAUNCH_CHECK();
-  return 0;
+  return detect_level_entry<false>("detect_level", x, ldx, n_img, H, W, K, wp, nat, bias, na, no, anchors, stride, p, z, zrows, zoff, 1.f, 0, 0.f, dtype,
+                                   stream);
+}
+
+extern "C" int ly_detect_level_aug(const void* x, int ldx, int n_img, int H, int W, int K, const void* wp, int nat, const float* bias, int na, int no,
+                                   const float* anchors, float stride, float* p, float* z, long zrows, long zoff, float dscale, int dflip, float img_w,
+                                   int dtype, void* stream) {
+  return detect_level_entry<true>("detect_level_aug", x, ldx, n_img, H, W, K, wp, nat, bias, na, no, anchors, stride, p, z, zrows, zoff, dscale, dflip,
+                                  img_w, dtype, stream);
 }
 
 extern "C" int ly_detect_level_ok(int K, int na, int no, int dtype) {

@@ -25,13 +25,22 @@ def _pick_parts(bs, dtype=torch.float32):
 
 class GraphedForward:
     """g = GraphedForward(model, example);  (z, [p3, p4, p5]) = g(x)  replays the captured forward on x (same shape / dtype as
-    example).  The returned tensors are the graph's static outputs: consume or copy them before the next call."""
+    example).  The returned tensors are the graph's static outputs: consume or copy them before the next call.
+    augment=True captures the augmented inference forward instead, (z, None) = g(x): the resampling launch, then its three passes on three
+    streams (the passes replace the sub-batches: `parts` is 1 and the per-layer forks stay off), joined before z is read."""
 
-    def __init__(self, model, example, parts=None, warmup=2):
+    def __init__(self, model, example, parts=None, warmup=2, augment=False):
         if model.training:
             raise RuntimeError("GraphedForward captures the inference forward: call model.eval() first")
         self.model = model
         self.x = example.clone()
+        self.augment = bool(augment)
+        if self.augment:
+            if parts not in (None, 1):
+                raise ValueError("augment=True runs its passes side by side: parts must be 1")
+            self.parts = 1
+            self._capture_augmented(model, warmup, example)
+            return
         bs = example.shape[0]
         self.parts = parts = _pick_parts(bs, example.dtype) if parts is None else parts
         if bs % parts:
@@ -105,6 +114,25 @@ class GraphedForward:
                 self.out = (torch.cat([o[0] for o in outs], 0), [torch.cat([o[1][i] for o in outs], 0) for i in range(len(outs[0][1]))])
             else:                                                                  # export mode: (z,)
                 self.out = (torch.cat([o[0] for o in outs], 0),)
+
+    def _capture_augmented(self, model, warmup, example):
+        cur = torch.cuda.current_stream()
+        with torch.no_grad():
+            for _ in range(warmup):                             # weight packing caches, allocator pools
+                model(self.x, augment=True)
+            passes = model.augment_plan(*example.shape[2:])["passes"]
+            self.streams = [torch.cuda.Stream(device=example.device) for _ in passes]
+            for s in self.streams:
+                s.wait_stream(cur)
+            torch.cuda.synchronize(example.device)
+            self.graph = torch.cuda.CUDAGraph()
+            from . import modules
+            keep, modules.FORK_BRANCHES = modules.FORK_BRANCHES, False     # no nested forks (see _warm_and_capture)
+            try:
+                with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+                    self.out = model._forward_augment(self.x, streams=self.streams)
+            finally:
+                modules.FORK_BRANCHES = keep
 
     def __call__(self, x=None):
         if x is not None and x.data_ptr() != self.x.data_ptr():

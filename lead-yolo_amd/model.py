@@ -198,10 +198,135 @@ class DetectionModel(nn.Module):
                 mod.lazy = bool(on)
 
     def forward(self, x, augment=False, profile=False, visualize=False):
-        if augment or profile or visualize:
-            raise NotImplementedError("augmented inference / per-layer profiling / feature visualisation are host-side tools "
-                                      "outside the hot path")
+        if profile or visualize:
+            raise NotImplementedError("per-layer profiling / feature visualisation are host-side tools outside the hot path")
+        if augment:
+            return self._forward_augment(x)
         return self._forward_once(x)
+
+    # ---- test-time augmentation (models/yolo.py DetectionModel._forward_augment, _descale_pred, _clip_augmented) -------------------------
+    TTA_SCALES = (1, 0.83, 0.67)
+    TTA_FLIPS = (None, 3, None)             # 3 = left-right
+
+    def augment_plan(self, h, w):
+        """The passes of augmented inference for an h x w input, from the reference's arithmetic alone (no tensors): per pass its scale and
+        flip, the resized size (hs, ws) and padded size (ho, wo) of utils/torch_utils.py scale_img(same_shape=False, gs=stride.max()), the
+        Detect levels whose rows survive _clip_augmented and the first row of each in the concatenated output [bs, rows, no].
+        h and w must be multiples of the largest stride: every pass's grids then halve exactly and _clip_augmented drops one whole level at
+        each end (the scale-1 pass's last, the smallest pass's first)."""
+        det = self.model[-1]
+        if not isinstance(det, M.Detect):
+            raise NotImplementedError("augmented inference needs a Detect head")
+        strides = [int(v) for v in det._strides()]
+        gs = max(strides)
+        h, w = int(h), int(w)
+        if h % gs or w % gs or h <= 0 or w <= 0:
+            raise ValueError(f"augmented inference: input {h} x {w} must be a multiple of the largest stride {gs}")
+        passes = []
+        for si, fi in zip(self.TTA_SCALES, self.TTA_FLIPS):
+            if si == 1.0:
+                hs, ws, ho, wo = h, w, h, w
+            else:
+                hs, ws = int(h * si), int(w * si)
+                ho, wo = (math.ceil(v * si / gs) * gs for v in (h, w))
+            rows = [det.na * (ho // s) * (wo // s) for s in strides]
+            passes.append(dict(scale=float(si), flip=fi == 3, resized=(hs, ws), size=(ho, wo), level_rows=rows))
+        # _clip_augmented: y[0] loses its last (rows0 // g) rows, y[-1] its first (rowsN // g) * 4 ** (nl - 1); both are whole levels
+        g = sum(4 ** k for k in range(det.nl))
+        cut0 = sum(passes[0]["level_rows"]) // g
+        cutN = (sum(passes[-1]["level_rows"]) // g) * 4 ** (det.nl - 1)
+        if passes[0]["level_rows"][-1] != cut0 or passes[-1]["level_rows"][0] != cutN:
+            raise ValueError(f"augmented inference: {h} x {w} does not clip to whole Detect levels")
+        base = 0
+        for k, ps in enumerate(passes):
+            keep = list(range(det.nl))
+            if k == 0:
+                keep = keep[:-1]
+            if k == len(passes) - 1:
+                keep = keep[1:]
+            offs, o = {}, base
+            for i in keep:
+                offs[i], o = o, o + ps["level_rows"][i]
+            ps.update(levels=tuple(keep), offset=base, offsets=offs, rows=o - base)
+            base = o
+        return dict(img=(h, w), passes=passes, rows=base)
+
+    def _dead_layers(self, levels):
+        """indices of the layers a pass that keeps only the Detect levels `levels` need not run: every layer whose output reaches no kept level
+        through the m.f routing (cached per level set)"""
+        cache = self.__dict__.setdefault("_dead_plan", {})
+        key = tuple(sorted(levels))
+        if key not in cache:
+            det = self.model[-1]
+            need, todo = set(), [det.f[i] % det.i for i in key]
+            while todo:
+                j = todo.pop()
+                if j in need:
+                    continue
+                need.add(j)
+                m = self.model[j]
+                for src in ([m.f] if isinstance(m.f, int) else list(m.f)):
+                    src = j - 1 if src == -1 else (src if src >= 0 else j + src)
+                    if src >= 0:
+                        todo.append(src)
+            cache[key] = frozenset(m.i for m in self.model if m is not det and m.i not in need)
+        return cache[key]
+
+    def _forward_augment(self, x, streams=None):
+        """augmented inference: (z [bs, rows, no], None) with the reference's rows (scale 1, 0.83 flipped, 0.67, clipped).  One ly_scale_img
+        launch makes both resized images; each pass runs only the layers and Detect levels whose rows are kept, and its levels write
+        descaled rows straight into z.  streams (graph.GraphedForward): one stream per pass, joined before z is returned."""
+        if self.training:
+            raise RuntimeError("augment=True is augmented INFERENCE: call model.eval() first (training-time augmentation is the dataloader's)")
+        if not isinstance(x, torch.Tensor) or not x.is_floating_point():
+            raise TypeError(f"augment=True takes a floating-point image batch (the reference passes im.float() / 255), got "
+                            f"{x.dtype if isinstance(x, torch.Tensor) else type(x).__name__}")
+        if x.dim() != 4 or not x.is_cuda:
+            raise RuntimeError(f"augment=True: a CUDA/ROCm NCHW image batch expected (got {tuple(x.shape)} on {x.device}); there is no CPU fallback")
+        from . import ops
+        det = self.model[-1]
+        plan = self.augment_plan(x.shape[2], x.shape[3])
+        scaled = [ps for ps in plan["passes"] if ps["scale"] != 1.0]
+        imgs = iter(ops.scale_img(x, [(*ps["resized"], *ps["size"], ps["flip"]) for ps in scaled]))
+        z = torch.empty((x.shape[0], plan["rows"], det.no), dtype=torch.float32, device=x.device)
+        main = torch.cuda.current_stream()
+        for k, ps in enumerate(plan["passes"]):
+            xi = x if ps["scale"] == 1.0 else next(imgs)
+            if streams is None:
+                self._forward_pass(xi, ps, z, plan["img"][1])
+                continue
+            streams[k].wait_stream(main)
+            with torch.cuda.stream(streams[k]):
+                self._forward_pass(xi, ps, z, plan["img"][1])
+        for s in streams or ():
+            main.wait_stream(s)
+        return z, None
+
+    def _forward_pass(self, x, ps, z, img_w):
+        """one pass of the augmented forward (_forward_once's routing without the dead layers); the kept Detect levels are launched as soon
+        as their feature maps exist"""
+        from . import ops
+        det = self.model[-1]
+        dead = self._dead_layers(ps["levels"])
+        ho, wo = ps["size"]
+        hw = [(ho // int(s), wo // int(s)) for s in det._strides()]
+        st = det.begin(x.shape[0], hw, x.device, z=z, zbase=ps["offset"], levels=ps["levels"], descale=(ps["scale"], ps["flip"], float(img_w)))
+        feeds = {det.f[i] % det.i: i for i in ps["levels"]}
+        y = []
+        for m in self.model:
+            if m is det:
+                break
+            if m.i in dead:
+                y.append(None)
+                continue
+            if m.f != -1:
+                x = y[m.f] if isinstance(m.f, int) else [x if j == -1 else y[j] for j in m.f]
+            x = m(x)
+            y.append(x if m.i in self.save else None)
+            if m.i in feeds:                                # as Detect.forward: the dtype policy at its edge, then no autocast
+                t = ops.edge_in(x, "Detect", det)[0] if isinstance(x, torch.Tensor) else x
+                with torch.autocast("cuda", enabled=False):
+                    det.level(st, feeds[m.i], t)
 
     def _forward_once(self, x):
         y = []

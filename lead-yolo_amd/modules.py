@@ -1117,10 +1117,22 @@ class Detect(nn.Module):
         return out if self.training else (z,) if self.export else (z, out)
 
     # ---- per-level API (lets the model launch a level as soon as its feature map exists) -----------------
-    def begin(self, bs, hw, device):
-        """allocate the outputs for feature maps of sizes hw[i] = (ny, nx); returns the state `level` fills"""
-        decode = not self.training
+    def begin(self, bs, hw, device, z=None, zbase=0, levels=None, descale=None):
+        """allocate the outputs for feature maps of sizes hw[i] = (ny, nx); returns the state `level` fills.
+        A pass of the augmented forward (DetectionModel._forward_augment) passes its own z [bs, rows, no] instead: the decoded rows of the levels
+        in `levels` (in level order) go to rows zbase.. of z, descaled by descale = (scale, flip, image width) (_descale_pred), and no raw maps
+        are written."""
         rows = [self.na * ny * nx for ny, nx in hw]
+        if z is not None:
+            keep = tuple(range(self.nl)) if levels is None else tuple(sorted(levels))
+            assert tuple(z.shape[::2]) == (bs, self.no) and z.dtype == torch.float32 and z.is_contiguous() and descale is not None
+            offs, o = [None] * self.nl, zbase
+            for i in keep:
+                offs[i], o = o, o + rows[i]
+            assert o <= z.shape[1]
+            return dict(z=z, zrows=z.shape[1], offs=offs, hw=[tuple(v) for v in hw], p=[None] * self.nl, bs=bs, device=device, forked=False,
+                        levels=keep, descale=tuple(descale))
+        decode = not self.training
         ext = getattr(self, "_out", None)                       # caller-provided output storage (graph.GraphedForward: batch slices)
         if ext is not None and decode:
             z = ext["z"]
@@ -1140,6 +1152,10 @@ class Detect(nn.Module):
             ctx.__enter__()
         try:
             ny, nx = st["hw"][i]
+            aug = st.get("descale")
+            if aug is not None:                             # augmented pass: descaled rows only
+                self._level_aug(st, i, xi, ny, nx, aug)
+                return
             ext = getattr(self, "_out", None)
             p = ext["p"][i] if ext is not None else torch.empty((st["bs"], self.na, ny, nx, self.no), dtype=torch.float32, device=st["device"])
             fused = self._fused_level_input(i, xi)
@@ -1157,6 +1173,21 @@ class Detect(nn.Module):
         finally:
             if side:
                 ctx.__exit__(None, None, None)
+
+    def _level_aug(self, st, i, xi, ny, nx, aug):
+        """level i of an augmented pass: ly_detect_level_aug, or the head GEMM + ly_detect_tail_aug where the one-launch kernel is not built"""
+        if st["offs"][i] is None:
+            raise ValueError(f"Detect level {i} is not among the levels {st['levels']} this pass writes")
+        scale, flip, img_w = aug
+        fused = self._fused_level_input(i, xi)
+        if fused is not None:
+            wp, b = self._packed_nat(i, ops.planes_of(xi))
+            ops.detect_level_aug(fused[0], fused[1], st["bs"], ny, nx, self.m[i].in_channels, wp, b, self.na, self.no, self.anchors[i],
+                                 self._strides()[i], st["z"], st["zrows"], st["offs"][i], scale, flip, img_w)
+        else:
+            buf, ldo = self._head(i, xi)
+            ops.detect_tail_aug(buf, ldo, st["bs"], ny, nx, self.na, self.no, self.anchors[i], self._strides()[i], st["z"], st["zrows"],
+                                st["offs"][i], scale, flip, img_w)
 
     def _make_grid(self, nx=20, ny=20, i=0):
         d, t = self.anchors[i].device, self.anchors[i].dtype

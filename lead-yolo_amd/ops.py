@@ -538,6 +538,48 @@ def detect_level(x, ldx, n, h, w, k, wp, bias, na, no, anchors, stride, p, z, zr
                                               capi.dtype_code(x), capi.stream_ptr()), "ly_detect_level")
 
 
+def detect_tail_aug(y, ldy, n, h, w, na, no, anchors, stride, z, zrows, zoff, dscale, dflip, img_w):
+    """ly_detect_tail with the _descale_pred step of test-time augmentation on the decoded rows (no raw maps)"""
+    capi.check(capi.lib().ly_detect_tail_aug(_p(y), ldy, n, h, w, na, no, _p(anchors), float(stride), None, _p(z), zrows, zoff, float(dscale),
+                                             int(dflip), float(img_w), capi.dtype_code(y), capi.stream_ptr()), "ly_detect_tail_aug")
+
+
+def detect_level_aug(x, ldx, n, h, w, k, wp, bias, na, no, anchors, stride, z, zrows, zoff, dscale, dflip, img_w, nat=True):
+    """ly_detect_level with the _descale_pred step of test-time augmentation on the decoded rows: z[..., :4] / dscale, then x = img_w - x when
+    dflip; no raw maps"""
+    es = x.element_size()
+    with _Timed(f"ly_detect_level_kernel<{_tname(x)}, {k // 32}>", 2.0 * n * h * w * k * 32, es * n * h * w * k + 4.0 * n * h * w * na * no):
+        capi.check(capi.lib().ly_detect_level_aug(_p(x), ldx, n, h, w, k, _p(wp), int(nat), _p(bias), na, no, _p(anchors), float(stride), None, _p(z),
+                                                  zrows, zoff, float(dscale), int(dflip), float(img_w), capi.dtype_code(x), capi.stream_ptr()),
+                   "ly_detect_level_aug")
+
+
+SCALE_IMG_PAD = 0.447       # utils/torch_utils.py scale_img: F.pad(value=0.447)
+_IMG_DTYPES = {torch.float32: capi.LY_F32, torch.bfloat16: capi.LY_BF16, torch.float16: capi.LY_F16}
+
+
+def scale_img(x, specs, pad=SCALE_IMG_PAD):
+    """The resampled passes of test-time augmentation in ONE launch (ly_scale_img): x NCHW [n, c, h, w] (float32 / bfloat16 / float16);
+    specs = [(hs, ws, ho, wo, flip)]: (x.flip(3) if flip else x) bilinearly resized to hs x ws (F.interpolate, align_corners=False) in the
+    top-left corner of an ho x wo canvas of `pad`.  Returns the list of outputs, contiguous NCHW, x's dtype."""
+    if not x.is_cuda:
+        raise RuntimeError(f"scale_img: the HIP path needs a CUDA/ROCm tensor (got {x.device}); there is no CPU fallback")
+    if x.dtype not in _IMG_DTYPES or x.dim() != 4:
+        raise TypeError(f"scale_img: a float32 / bfloat16 / float16 NCHW image batch expected (got {x.dtype}, {tuple(x.shape)})")
+    if not 1 <= len(specs) <= capi.SCALE_IMG_MAX:
+        raise ValueError(f"scale_img: 1..{capi.SCALE_IMG_MAX} outputs per launch (got {len(specs)})")
+    x = x.contiguous()
+    n, c, h, w = x.shape
+    outs = [torch.empty((n, c, ho, wo), dtype=x.dtype, device=x.device) for (_, _, ho, wo, _) in specs]
+    arr = (capi.LyScaleImgSpec * len(specs))(*[capi.LyScaleImgSpec(o.data_ptr(), hs, ws, ho, wo, int(bool(fl)))
+                                               for o, (hs, ws, ho, wo, fl) in zip(outs, specs)])
+    tn = {torch.float32: "float", torch.bfloat16: "__bf16", torch.float16: "_Float16"}[x.dtype]
+    # algorithmic bytes: the source once per output, every output element once
+    with _Timed(f"ly_scale_img_kernel<{tn}>", 0.0, x.element_size() * sum(n * c * (h * w + ho * wo) for (_, _, ho, wo, _) in specs)):
+        capi.check(capi.lib().ly_scale_img(_p(x), n, c, h, w, arr, len(specs), float(pad), _IMG_DTYPES[x.dtype], capi.stream_ptr()), "ly_scale_img")
+    return outs
+
+
 def detect_head_bwd(dp, n, h, w, na, no, du, ldu, dbias):
     """dp fp32 [n, na, h, w, no] -> du rows [n*h*w, ldu] (columns >= na*no zero), dbias[na*no] += column sums (dbias fp32, or a float64
     scratch of small_grad_scratch)"""
