@@ -19,7 +19,7 @@ extern "C" {
 #endif
 
 enum { LY_F32 = 0, LY_BF16 = 1 };
-int ly_abi_version(void);      /* 3: ly_adam_step (2: dtype-polymorphic entry points) */
+int ly_abi_version(void);      /* 5: ly_mosaic_img / ly_mosaic_labels (4: augmented inference, 3: ly_adam_step, 2: dtype-polymorphic entry points) */
 const char* ly_last_error(void);
 
 /* FasterNet MLPBlock forward, eval form (BN folded to scale/shift):
@@ -314,6 +314,46 @@ typedef struct LyScaleImgSpec {
   int flip;               /* != 0: resample x.flip(3)                                                 */
 } LyScaleImgSpec;
 int ly_scale_img(const void* x /*T*/, int n_img, int C, int H, int W, const LyScaleImgSpec* specs, int nspec, float pad, int dtype, void* stream);
+
+/* ---- training augmentation on the device (csrc/ly_mosaic.hip; utils/dataloaders.py LoadImagesAndLabels.__getitem__ with augment=True) ----
+ * The image bank holds every training image as load_image returns it (uint8 HWC BGR, long side resized) back to back; a tile addresses one
+ * image by its byte offset (64-bit: a decoded dataset is several GB).  A LyMosaicImage describes one output image of the batch:
+ *   mosaic != 0: load_mosaic's four tiles on a 2s x 2s canvas filled with 114, then random_perspective with border -s/2;
+ *   mosaic == 0: letterbox(auto=False) of one image onto s x s (tile[0]; tile[1..3].src = -1), then random_perspective with border 0;
+ * then augment_hsv (lut != NULL), flipud, fliplr.                                                                                          */
+typedef struct LyMosaicTile {
+  long off;               /* byte offset of the source image in the bank                                                */
+  int h, w;               /* source image size (pixels)                                                                 */
+  int x1a, y1a, x2a, y2a; /* placement rectangle on the canvas: columns [x1a, x2a), rows [y1a, y2a); empty when src = -1 */
+  int x1b, y1b;           /* source pixel at the rectangle's top-left corner                                            */
+  int lab, nlab;          /* first row and count of the source's labels in the label bank                                */
+  int src;                /* bank index of the source image, -1: no tile                                                */
+  int unused;
+  double padw, padh;      /* label offsets: x1a - x1b, y1a - y1b (mosaic); letterbox: the float half-pads (dw, dh)      */
+} LyMosaicTile;
+typedef struct LyMosaicImage {
+  LyMosaicTile tile[4];   /* mosaic: top-left, top-right, bottom-left, bottom-right (load_mosaic's order)               */
+  double m[6];            /* random_perspective's M[:2] (canvas -> output), float64: labels                              */
+  float minv[6];          /* its inverse (output -> canvas), inverted in float64 on the host, fp32: pixels               */
+  double scale;           /* random_perspective's scale draw (box_candidates' box1 = box * scale)                        */
+  int mosaic;             /* != 0: four tiles, labels clipped to [0, 2s] before the warp                                 */
+  int flipud, fliplr;     /* applied after the warp and the HSV step                                                     */
+  int unused;
+  const unsigned char* lut; /* device [3][256]: augment_hsv's hue / saturation / value LUTs; NULL: no HSV step           */
+} LyMosaicImage;
+/* out [n_img, 3, s, s] uint8, RGB planes: per pixel, (u, v) mirrored by the flips, the canvas point X = minv[0]*u + minv[1]*v + minv[2],
+ * Y = minv[3]*u + minv[4]*v + minv[5] (fp32), four bilinear taps of the canvas (114 outside every rectangle), one rounding (int)(acc + 0.5f);
+ * then, with lut, OpenCV's 8-bit BGR2HSV, the LUTs and OpenCV's float HSV2BGR.  Replaces load_mosaic / letterbox + random_perspective
+ * (cv2.warpAffine, borderValue 114) + augment_hsv + np.flipud / np.fliplr + transpose((2, 0, 1))[::-1] (utils/dataloaders.py, utils/augmentations.py).
+ * imgs: DEVICE table of n_img entries.  s a multiple of 16, out 16-byte aligned.                                                        */
+int ly_mosaic_img(const unsigned char* bank, const LyMosaicImage* imgs, int n_img, int s, unsigned char* out, void* stream);
+/* targets [cap][6] fp32: the batch's label rows (image, cls, x, y, w, h) as __getitem__ + collate_fn produce them — xywhn2xyxy with the
+ * tile's pads, the 2s clip (mosaic), the corners through m, min / max, clip to [0, s], box_candidates(wh_thr 2, ar_thr 100, area_thr 0.10),
+ * xyxy2xywhn(clip, eps 1e-3), the flips — float64 arithmetic, one rounding on store.  Survivors image-major, in tile and file order;
+ * rows [count, cap) are padding (-1, 0, 0, 0, 0, 0).  labels: the label bank [rows][5] float64 (cls, normalised xywh); max_labels = the
+ * largest nlab of any tile; cap >= n_img * 4 * max_labels.  Replaces the label arithmetic of load_mosaic / random_perspective /
+ * __getitem__ and collate_fn (utils/dataloaders.py, utils/augmentations.py).  One block.                                                   */
+int ly_mosaic_labels(const double* labels, const LyMosaicImage* imgs, int n_img, int s, int max_labels, float* targets, long cap, void* stream);
 /* Adjoint of that permute for the training step (models/yolo.py:88): dp fp32 [n, na, H, W, no] -> du rows [n*H*W][ldu] of T (column a*no+o;
  * columns >= na*no written as zero: the operand of the head's dgrad / wgrad), dbias[a*no+o] += sum over pixels.  W <= 160, na*no <= ldu <= 32. */
 int ly_detect_head_bwd(const float* dp, int n_img, int H, int W, int na, int no, void* du /*T*/, int ldu, float* dbias,

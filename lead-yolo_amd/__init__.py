@@ -11,3 +11,4 @@ from .train import GraphedTrainStep, ModelEMA, forward_backward, optimizer_step,
 from .optim import FusedAdam, FusedAdamW, FusedSGD  # noqa: F401
 from .graph import GraphedForward  # noqa: F401
 from .nms import nms_padded, non_max_suppression  # noqa: F401,E402
+from .mosaic import ImageBank, MosaicAugment  # noqa: F401,E402

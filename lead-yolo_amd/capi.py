@@ -75,6 +75,16 @@ class LyScaleImgSpec(ctypes.Structure):
     _fields_ = [("out", _P), ("Hs", _I), ("Ws", _I), ("Ho", _I), ("Wo", _I), ("flip", _I)]
 
 
+class LyMosaicTile(ctypes.Structure):
+    _fields_ = [("off", _L), ("h", _I), ("w", _I), ("x1a", _I), ("y1a", _I), ("x2a", _I), ("y2a", _I), ("x1b", _I), ("y1b", _I),
+                ("lab", _I), ("nlab", _I), ("src", _I), ("unused", _I), ("padw", ctypes.c_double), ("padh", ctypes.c_double)]
+
+
+class LyMosaicImage(ctypes.Structure):
+    _fields_ = [("tile", LyMosaicTile * 4), ("m", ctypes.c_double * 6), ("minv", _F * 6), ("scale", ctypes.c_double), ("mosaic", _I),
+                ("flipud", _I), ("fliplr", _I), ("unused", _I), ("lut", _P)]
+
+
 class LyPackDesc(ctypes.Structure):
     _fields_ = [("src", _P), ("dst", _P), ("r_valid", _I), ("K", _I), ("planes", _I), ("S", _I), ("t0", _I), ("T", _I),
                 ("nrb", _I), ("nb", _I), ("nc", _I), ("vb", _I), ("vc", _I),
@@ -183,6 +193,8 @@ SIGNATURES = {
     "ly_detect_tail_aug": [_P, _I, _I, _I, _I, _I, _I, _P, _F, _P, _P, _L, _L, _F, _I, _F, _I, _P],
     "ly_detect_level_aug": [_P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _F, _P, _P, _L, _L, _F, _I, _F, _I, _P],
     "ly_scale_img": [_P, _I, _I, _I, _I, ctypes.POINTER(LyScaleImgSpec), _I, _F, _I, _P],
+    "ly_mosaic_img": [_P, _P, _I, _I, _P, _P],
+    "ly_mosaic_labels": [_P, _P, _I, _I, _I, _P, _L, _P],
     "ly_detect_head_bwd": [_P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P],
     "ly_f64_add": [ctypes.POINTER(LyF64AddTable), _P],
     "ly_pack_table": [_P, _P, _I, _P],

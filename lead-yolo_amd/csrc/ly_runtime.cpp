@@ -14,7 +14,7 @@ extern "C" void ly_set_error(const char* fmt, ...) {
 
 extern "C" const char* ly_last_error(void) { return g_err; }
 
-extern "C" int ly_abi_version(void) { return 4; }
+extern "C" int ly_abi_version(void) { return 5; }
 
 // ---- stream events that cross a hipGraph boundary (data-parallel step) ---------------------------------
 // A replayed graph of forward + backward must release the gradient exchange of a bucket the moment the bucket's last gradient kernel
