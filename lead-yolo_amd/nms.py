@@ -12,8 +12,7 @@ MAX_WH = 7680        # utils/general.py:918
 MAX_NMS = 30000      # utils/general.py:919
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
+_p = capi.ptr
 
 
 def nms_padded(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, max_det=300, multi_label=False):

@@ -1,9 +1,5 @@
 """Host side of the fused Adam / AdamW optimisers (CPU): smart_optimizer builds the reference's torch objects for every name it knows
-(utils/torch_utils.py:318-346), the fused classes refuse what their kernel does not implement, and the C-ABI entry struct mirrors the
-header."""
-import os
-import re
-
+(utils/torch_utils.py:318-346) and the fused classes refuse what their kernel does not implement."""
 import pytest
 import torch
 
@@ -71,20 +67,3 @@ def test_fused_adam_state_dict_loads_into_torch_adamw_and_back():
     assert fused._T == 2 and fused._step0[ps[0]] == 0 and ps[1] not in fused._step0
     back = fused.state_dict()
     assert set(back["state"]) == {0, 2} and float(back["state"][0]["step"]) == 2.0 and back["state"][0]["step"].dtype == torch.float32
-
-
-def test_adam_tensor_struct_matches_header_field_order():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdr = open(os.path.join(root, "include", "lead_yolo_hip.h")).read()
-    cls = L.capi.LyAdamTensor
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cls.__name__, cls.__name__), hdr, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            names.append(re.findall(r"([A-Za-z_][A-Za-z0-9_]*)\s*$", part.strip())[0])
-    assert names == [f[0] for f in cls._fields_]
-    assert "ly_adam_step" in L.capi.SIGNATURES

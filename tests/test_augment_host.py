@@ -2,8 +2,6 @@
 and the C ABI of the new kernels."""
 import ctypes
 import math
-import os
-import re
 
 import pytest
 
@@ -94,24 +92,6 @@ def test_augment_entry_points_exported():
         assert hasattr(lib, name), name
         assert name in L.capi.SIGNATURES
     assert L.capi.lib().ly_abi_version() >= 4
-
-
-def test_scale_img_struct_matches_header_field_order():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdr = open(os.path.join(root, "include", "lead_yolo_hip.h")).read()
-    cls = L.capi.LyScaleImgSpec
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cls.__name__, cls.__name__), hdr, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            names.append(re.findall(r"([A-Za-z_][A-Za-z0-9_]*)\s*$", part.strip())[0])
-    assert names == [f[0] for f in cls._fields_]
-    assert int(re.search(r"#define LY_SCALE_IMG_MAX (\d+)", hdr).group(1)) == L.capi.SCALE_IMG_MAX
-    assert int(re.search(r"LY_F16 = (\d+)", hdr).group(1)) == L.capi.LY_F16
 
 
 def test_augment_input_errors_on_host(model_s):

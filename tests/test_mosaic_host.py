@@ -1,10 +1,7 @@
 """Host side of the on-device training augmentation (lead-yolo_amd/mosaic.py): the parameter table MosaicAugment builds, against the
 reference formulas restated here in float64 numpy (utils/dataloaders.py load_mosaic, utils/augmentations.py letterbox / random_perspective /
 augment_hsv, torch's DistributedSampler).  No GPU."""
-import ctypes
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -244,26 +241,3 @@ def test_bank_layout_and_rgb():
     b2 = L.ImageBank.from_dataset(DS(), device="cpu")
     assert b2.max_labels == 1 and b2.labels.dtype == torch.float64 and tuple(b2.labels.shape) == (3, 5)
     np.testing.assert_array_equal(b2.data.numpy()[:32 * 20 * 3], ims[0].reshape(-1))
-
-
-def _struct_fields(hdr, name):
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = re.sub(r"\[\d+\]", "", decl.strip())
-        if decl:
-            names += [re.findall(r"([A-Za-z_][A-Za-z0-9_]*)\s*$", part.strip())[0] for part in decl.split(",")]
-    return names
-
-
-def test_mosaic_abi():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdr = open(os.path.join(root, "include", "lead_yolo_hip.h")).read()
-    for cls in (L.capi.LyMosaicTile, L.capi.LyMosaicImage):
-        assert _struct_fields(hdr, cls.__name__) == [f[0] for f in cls._fields_], cls.__name__
-    assert ctypes.sizeof(L.capi.LyMosaicTile) == 72 and ctypes.sizeof(L.capi.LyMosaicImage) == 392      # static_assert in ly_mosaic.hip
-    lib = ctypes.CDLL(L.capi.LIB_PATH)
-    for name in ("ly_mosaic_img", "ly_mosaic_labels"):
-        assert hasattr(lib, name) and name in L.capi.SIGNATURES
-    assert L.capi.lib().ly_abi_version() == 5
