@@ -100,7 +100,13 @@ __global__ __launch_bounds__(LY_THREADS) void ly_loss_match_kernel(const LyLossL
   const int b = (int)tg[0];
   const bool padding = tg[0] == -1.f;                     // a row with image index exactly -1 is PADDING (fixed-shape target
                                                           // buffers of a captured step): ignored silently
-  const bool sane = tg[0] >= 0.f && b < L.bs && gx == gx && gy == gy && gw == gw && gh == gh;
+  // nc > 1: the class column selects the positive class.  The reference's `t[range(n), tcls[i]] = cp` raises for an index >= nc; a negative
+  // index -k wraps there to class nc - k (torch indexing) — a deliberate difference: a negative class is a corrupt label here, not a way
+  // to count classes from the end.  A class whose truncation (.long()) is outside [0, nc), or a NaN, would train every class of the row as
+  // a negative (NaN: class 0 as the positive): such a row is rejected and counted like a bad image index.  nc = 1 never reads the column.
+  const float cf = tg[1];
+  const bool cls_ok = L.no - 5 <= 1 || (cf > -1.f && cf < (float)(L.no - 5));
+  const bool sane = tg[0] >= 0.f && b < L.bs && gx == gx && gy == gy && gw == gw && gh == gh && cls_ok;
   if (!sane && !padding && k == 0 && a == 0) atomicAdd(L.acc + 3, 1.f);
   bool ok = sane && fmaxf(fmaxf(rw, 1.f / rw), fmaxf(rh, 1.f / rh)) < L.anchor_t;
   const float g = 0.5f;

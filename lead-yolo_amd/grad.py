@@ -656,6 +656,12 @@ def detect_head(det, i, wp, x, weight, bias):
     n, _, h, w = x.shape
     if w <= DetectHeadFn.MAXW and (co + 7) // 8 * 8 <= DetectHeadFn.MAXLD and bias is not None:
         return DetectHeadFn.apply(det, i, wp, x, weight, bias)
+    if x.dtype == torch.bfloat16:
+        # the generic conv node stores its output in the storage type: a bf16 head output would round the raw map (up to 2^-8 of the value)
+        # on its way to the loss and sum the bias gradient from a bf16 du.  The map is widened (exact; autograd rounds dx back to bf16) and
+        # the head runs in fp32 storage, like Detect._head in eval.  Cost not measured: the copy and an fp32 contraction per level.
+        x = x.float()
+        wp, _ = det._packed(i, 2)
     y = conv_bn_act(ConvSpec("pw", co), wp, x, None, weight, bias, None)
     p = torch.empty((n, det.na, h, w, det.no), dtype=torch.float32, device=y.device)
     p.copy_(y.view(n, det.na, det.no, h, w).permute(0, 1, 3, 4, 2))

@@ -6,6 +6,11 @@ the gradient, with no host sync.
 There is no torch formulation in this package: the CPU restatement used for checking lives in oracle/functional.py
 (test infrastructure).  `ComputeLoss` therefore needs CUDA predictions and raises otherwise.  Any nc: the class BCE of
 utils/loss.py:168-173 (label smoothing, cls_pw) is part of the kernel when nc > 1 (LEAD-YOLO.yaml itself is nc = 1); obj_pw too.
+A target row whose class column is outside [0, nc) after truncation, or NaN, is rejected when nc > 1 exactly like a row whose image index
+is outside the batch: the loss comes back NaN and `build_targets` raises IndexError.  The reference's `t[range(n), tcls[i]] = cp` raises
+for a class >= nc and wraps a negative class -k to nc - k; rejecting negatives too is a deliberate difference (a negative class is a corrupt
+label).  A silently accepted row would train all its classes as negatives.  nc = 1 never reads the class column, and padding rows
+(image index -1) stay silent whatever their class column holds.
 `build_targets` is the inspectable view of the kernel's anchor matching: it runs the matching kernel alone and reads its candidate buffers back (int64 indices bit-exact with the reference's vectors, tests/test_loss.py).
 """
 import torch
@@ -86,7 +91,7 @@ class ComputeLoss:
         preds = [t.detach().float().contiguous() for t in p]
         r = self._levels(preds, targets, match_only=True)
         if float(r["acc"][:, 3].sum()) > 0:
-            raise IndexError("build_targets: a target row has an image index outside the batch (or a NaN)")
+            raise IndexError("build_targets: a target row has an image index outside the batch, a class outside [0, nc) (nc > 1), or a NaN")
         tcls, tbox, indices, anch = [], [], [], []
         nt = r["nt"]
         for i, pi in enumerate(preds):

@@ -1073,6 +1073,13 @@ class Detect(nn.Module):
     def _head(self, i, x):
         conv = self.m[i]
         L = Lazy.of(x)
+        if L.a0.dtype == torch.bfloat16:
+            # the GEMM stores in its own element type: a bf16 buffer would round the raw map (up to 2^-8 of the value) before the tail reads
+            # it, while ly_detect_level hands its fp32 accumulators on.  Raw maps leave Detect as fp32 on every route: the feature map is
+            # widened (exact) and the head contracts in fp32 storage.  The cost — a full fp32 copy of the map and a bf16x3 contraction for
+            # every level that misses the one-launch kernel (na*no > 32, Lazy inputs, misaligned rows; eval and augmented passes) — has not
+            # been measured (the benchmark runs nc = 1); a GEMM with a bf16 source and an fp32 destination would avoid the copy
+            L = Lazy.of((x.materialize() if isinstance(x, Lazy) else x).float())
         wp, b = self._packed(i, ops.planes_of(L.a0))
         ldo = (conv.out_channels + 3) // 4 * 4
         n, c, h, w = L.shape

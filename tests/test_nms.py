@@ -140,3 +140,199 @@ def test_hip_nms_edge_cases():
     # model in validation mode hands (inference_out, loss_out)
     out = L.non_max_suppression((one, None))
     assert out[0].shape == (1, 6)
+
+
+# ---- edges of ly_nms_greedy: truncation at max_nms, the bitset's tail word, max_det, exact score ties, class filters at nc >= 64 -----------
+# Every case below is compared bit for bit.  A pair whose IoU lies within rounding of iou_thres could legitimately flip between numpy and
+# the device (different contraction of the same fp32 expression), so a case only counts when the oracle's keep set is the same with the IoU
+# evaluated in float32 and in float64: `oracle_keep_stable` asserts that, on the CPU for every synthetic case and again inside each GPU test.
+def _nms64(boxes, scores, iou_thres):
+    """oracle.nms.nms with the IoU arithmetic in float64 (same fp32 boxes, same fp32 threshold)"""
+    boxes = boxes.astype(np.float64)
+    thr = np.float64(np.float32(iou_thres))
+    n = boxes.shape[0]
+    area = (boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1])
+    alive = np.ones(n, dtype=bool)
+    keep = []
+    for i in range(n):
+        if not alive[i]:
+            continue
+        keep.append(i)
+        j = np.arange(i + 1, n)[alive[i + 1:]]
+        if j.size == 0:
+            continue
+        iw = np.maximum(np.minimum(boxes[i, 2], boxes[j, 2]) - np.maximum(boxes[i, 0], boxes[j, 0]), 0.0)
+        ih = np.maximum(np.minimum(boxes[i, 3], boxes[j, 3]) - np.maximum(boxes[i, 1], boxes[j, 1]), 0.0)
+        inter = iw * ih
+        alive[j[inter / (area[i] + area[j] - inter) > thr]] = False
+    return np.asarray(keep, dtype=np.int64)
+
+
+def oracle_keep_stable(pred, conf, iou=0.45, **kw):
+    """the oracle's result, after asserting that its keep set does not depend on the precision of the IoU arithmetic"""
+    want, idx = ON.non_max_suppression(pred, conf, iou, **kw)
+    saved = ON.nms
+    ON.nms = _nms64
+    try:
+        _, idx64 = ON.non_max_suppression(pred, conf, iou, **kw)
+    finally:
+        ON.nms = saved
+    for a, b in zip(idx, idx64):
+        assert np.array_equal(a, b), "an IoU of this case is within rounding of the threshold: pick another seed"
+    return want, idx
+
+
+MAX_NMS_EDGE = ON.MAX_NMS
+
+
+def _keep_with_max_nms(pred, conf, max_nms, **kw):
+    """the oracle's kept indices with its cut moved to max_nms"""
+    saved = ON.MAX_NMS
+    ON.MAX_NMS = max_nms
+    try:
+        return ON.non_max_suppression(pred, conf, 0.45, **kw)[1]
+    finally:
+        ON.MAX_NMS = saved
+
+
+def _count_case(n, seed):
+    """one image, 30100 single-class boxes in 12 tight clusters, every score above the threshold; objectness 0 on all but n random rows"""
+    N = 30100
+    p = _random_pred(1, N, 1, seed)
+    g = np.random.default_rng(seed + 1)
+    p[..., 4] = g.uniform(0.1, 1.0, (1, N))
+    p[..., 5] = g.uniform(0.1, 1.0, (1, N))
+    perm = g.permutation(N)
+    p[0, perm[n:], 4] = 0.0
+    if n >= MAX_NMS_EDGE:
+        # the candidate with the lowest score stands alone, far from the clusters: nothing suppresses it, so it is kept exactly when the cut
+        # at max_nms leaves it in — rank 29999 (n = 30000) is inside, rank 30000 (n = 30001) is the first one outside
+        live = perm[:n]
+        last = live[np.argmin((p[0, live, 4] * p[0, live, 5]))]
+        p[0, last, 0:2] = 5000.0
+    return p
+
+
+def _grid_case(seed):
+    """1600 disjoint boxes: nobody suppresses anybody, max_det cuts"""
+    g = np.random.default_rng(seed)
+    yy, xx = np.meshgrid(np.arange(40), np.arange(40), indexing="ij")
+    p = np.zeros((1, 1600, 6), np.float32)
+    p[0, :, 0], p[0, :, 1] = xx.reshape(-1) * 16 + 8, yy.reshape(-1) * 16 + 8
+    p[0, :, 2:4] = g.uniform(4, 12, (1600, 2))
+    p[0, :, 4] = g.uniform(0.3, 1.0, 1600)
+    p[0, :, 5] = 1.0
+    return p
+
+
+def _first_takes_all_case(seed):
+    """row 700 has the top score; every other box is that box moved by a pixel or two: all suppressed by it"""
+    g = np.random.default_rng(seed)
+    p = np.zeros((1, 1500, 6), np.float32)
+    p[0, :, 0:2] = 300 + g.uniform(-2, 2, (1500, 2))
+    p[0, :, 2:4] = 100 + g.uniform(-2, 2, (1500, 2))
+    p[0, :, 4] = g.uniform(0.3, 0.9, 1500)
+    p[0, :, 5] = 1.0
+    p[0, 700, 4] = 0.95
+    return p
+
+
+def _tie_case(seed):
+    """600 rows = 200 boxes, each three times with the SAME score: once more on the spot (rows i and 200 + i overlap fully) and once 3000 px
+    away (row 400 + i, apart from both)"""
+    base = _random_pred(1, 200, 1, seed, cluster=False)
+    base[..., 0:2] = np.clip(base[..., 0:2], 50, 2500)
+    base[..., 4] = np.maximum(base[..., 4], 0.3)
+    base[..., 5] = 1.0
+    far = base.copy()
+    far[..., 0] += 3000
+    return np.concatenate((base, base.copy(), far), 1)
+
+
+_COUNT_CASES = [(1, 300), (31, 300), (32, 1), (33, 300), (255, 1000), (256, 300), (257, 300), (30000, 1000), (30001, 1000)]      # (max_det 1000: the walk must reach the last rank)
+
+
+def _edge_case(name):
+    """-> (pred, conf_thres, kwargs)"""
+    if name.startswith("count"):
+        n, max_det = (int(v) for v in name.split("-")[1:])
+        return _count_case(n, 500 + n), 0.001, dict(max_det=max_det)
+    if name.startswith("grid"):
+        return _grid_case(61), 0.25, dict(max_det=int(name.split("-")[1]))
+    if name == "first-takes-all":
+        return _first_takes_all_case(62), 0.25, dict(max_det=300)
+    if name == "ties":
+        return _tie_case(63), 0.25, dict(max_det=1000)
+    if name == "nc64-class63":
+        return _random_pred(2, 1500, 64, 64), 0.05, dict(classes=[63], max_det=300)
+    raise KeyError(name)
+
+
+EDGE_CASES = [f"count-{n}-{d}" for n, d in _COUNT_CASES] + ["grid-1", "grid-300", "grid-1000", "first-takes-all", "ties", "nc64-class63"]
+
+
+def _check_edge_premise(name, pred, conf, kw, idx):
+    """what makes the case mean something, from the oracle's side"""
+    if name.startswith("count"):
+        n = int(name.split("-")[1])
+        x = pred[0]
+        assert int(((x[:, 4] > conf) & (x[:, 4] * x[:, 5] > conf)).sum()) == n          # the candidate count the kernel sees
+        assert len(idx[0]) >= 1
+        if n >= MAX_NMS_EDGE:
+            # the position of the cut decides the result: one candidate fewer or more than max_nms = 30000 changes the kept set
+            lone = int(np.nonzero(x[:, 0] == 5000.0)[0][0])
+            assert (lone in idx[0].tolist()) == (n == MAX_NMS_EDGE)
+            other = _keep_with_max_nms(pred, conf, MAX_NMS_EDGE - 1 if n == MAX_NMS_EDGE else MAX_NMS_EDGE + 1, **kw)
+            assert (lone in other[0].tolist()) == (n != MAX_NMS_EDGE)
+            assert not np.array_equal(other[0], idx[0])
+    elif name.startswith("grid"):
+        assert len(idx[0]) == kw["max_det"]                                            # max_det is what stops it
+    elif name == "first-takes-all":
+        assert idx[0].tolist() == [700]
+    elif name == "ties":
+        k = set(idx[0].tolist())
+        assert len(k) > 100
+        for i in range(200):                                                           # of two identical rows the lower index; the far twin too
+            assert (200 + i) not in k
+            assert (i in k) == ((400 + i) in k)
+        assert sum(1 for i in range(200) if i in k) > 50
+    elif name == "nc64-class63":
+        assert sum(len(v) for v in idx) > 5
+
+
+@pytest.mark.parametrize("name", EDGE_CASES)
+def test_edge_case_premises_hold_in_the_oracle(name):
+    """CPU: every synthetic edge case keeps the same boxes with float32 and float64 IoU arithmetic, and does what its name says"""
+    pred, conf, kw = _edge_case(name)
+    _, idx = oracle_keep_stable(pred, conf, **kw)
+    _check_edge_premise(name, pred, conf, kw, idx)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", EDGE_CASES)
+def test_hip_nms_edges_match_oracle(name):
+    """ly_nms_greedy at candidate counts around the bitset's word (32) and block (256) sizes and around max_nms = 30000 (the lowest-scored candidate stands alone: at
+    30000 it is the last one inside the cut and kept, at 30001 it is cut before the walk — _check_edge_premise asserts that the oracle's
+    result changes when its cut moves by one), with max_det 1 / 300 / 1000, everything suppressed by the first box, nothing
+    suppressed at all, exact score ties (stable: ascending candidate index), and a class filter on the last representable class"""
+    import lead_yolo_amd as L
+    dev = torch.device("cuda:0")
+    pred, conf, kw = _edge_case(name)
+    want, want_idx = oracle_keep_stable(pred, conf, **kw)
+    _check_edge_premise(name, pred, conf, kw, want_idx)
+    pt = torch.from_numpy(pred).to(dev)
+    got = L.non_max_suppression(pt, conf, 0.45, **kw)
+    dets, count, keep = L.nms_padded(pt, conf, 0.45, **kw)
+    for b in range(pred.shape[0]):
+        assert int(count[b]) == len(want_idx[b])
+        assert keep[b, :len(want_idx[b])].cpu().tolist() == want_idx[b].tolist()
+        np.testing.assert_array_equal(got[b].cpu().numpy(), want[b])
+        assert float(dets[b, len(want_idx[b]):].abs().sum()) == 0.0
+
+
+@pytest.mark.gpu
+def test_hip_nms_class_filter_above_63_is_refused():
+    import lead_yolo_amd as L
+    pred = torch.from_numpy(_random_pred(1, 100, 80, 65)).to(torch.device("cuda:0"))
+    with pytest.raises(NotImplementedError):
+        L.non_max_suppression(pred, 0.05, 0.45, classes=[70])
