@@ -402,6 +402,26 @@ int ly_nms_candidates_ml(const float* pred, int bs, int N, int no, float conf_th
 int ly_nms_greedy(const float* det, const long* order, const float* sorted_score, int bs, int N, float iou_thres, float max_wh, int max_det,
                   int max_nms, int* keep, int* count, void* stream);
 
+/* ---- validation scoring on the device (csrc/ly_metrics.hip; val.py:79-101 process_batch, val.py:150-166 its per-image preparation) -------
+ * ly_val_match replaces val.py:79-101 and val.py:150-166 for a whole batch: one launch, one block per image b, results into slot
+ * cursor[0] + b of a caller-allocated accumulator of `capacity` slots (rows of `row_width` >= max_det entries).
+ *   dets [bs, max_det, 6] (xyxy, conf, cls) / counts [bs]: what nms_padded returns;  targets [nt, 6] = (image, class, x, y, w, h)
+ *   normalised, rows of one image in any order and place (NULL with nt = 0);  W, H: the network input size (val.py:217);
+ *   shapes NULL or [bs, 5] = (h0, w0, gain, padw, padh): labels and the matching copy of the boxes go through scale_boxes with
+ *   ratio_pad and clip_boxes (val.py:157-162);  levels: 10 device floats (val.py:171);  single_cls != 0: prediction class 0 (val.py:152).
+ *   Matching: a detection's best label is the label of its class with the largest IoU (> 0; the lowest targets row on equal IoU); at
+ *   level i it is correct iff that IoU >= levels[i] and no lower-indexed detection with the same best label passes level i.
+ *   Per slot row, zero past counts[b]: correct (uint16, bit i = level i), conf, cls, match_label (row of targets, -1: none), match_iou.
+ *   Per slot: n_det, nt_class [capacity, nc] (labels per class), overflow (bit 0: more than LY_VAL_MAX_LABELS labels — the image's
+ *   matching is skipped; bit 1: a label class outside [0, nc), not counted).  A slot >= capacity is not written.
+ * ly_val_advance replaces the `seen` bookkeeping of val.py:145-149: one thread adds bs to cursor[0], behind the match on the same stream,
+ * so that a captured pair replays batch after batch.                                                                                    */
+#define LY_VAL_MAX_LABELS 512
+int ly_val_match(const float* dets, const int* counts, int bs, int max_det, const float* targets, long nt, int W, int H, const float* shapes,
+                 const float* levels, int single_cls, int nc, const int* cursor, int capacity, int row_width, void* correct, float* conf,
+                 float* cls, int* match_label, float* match_iou, int* n_det, int* nt_class, int* overflow, void* stream);
+int ly_val_advance(int* cursor, int bs, void* stream);
+
 /* ---- backward building blocks of the training step (train.py:324 `scaler.scale(loss).backward()`) -------------
  * Data gradients of 1x1 / 3x3 stride-1 convolutions reuse ly_gemm_fwd / ly_conv3x3_fwd with transposed weights.   */
 

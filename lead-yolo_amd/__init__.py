@@ -12,3 +12,4 @@ from .optim import FusedAdam, FusedAdamW, FusedSGD  # noqa: F401
 from .graph import GraphedForward  # noqa: F401
 from .nms import nms_padded, non_max_suppression  # noqa: F401,E402
 from .mosaic import ImageBank, MosaicAugment  # noqa: F401,E402
+from .metrics import MatchAccumulator, Validator, ValResult, ap_per_class, compute_ap, match_padded, unpack_correct  # noqa: F401,E402
