@@ -906,7 +906,9 @@ def coordatt_train(mod, x):
     """CoordAtt.forward in training (models/common.py:1595-1609)."""
     n, c, h, w = x.shape
     params = (mod.conv1.weight, mod.conv1.bias, mod.bn1.weight, mod.bn1.bias, mod.conv_h.weight, mod.conv_h.bias, mod.conv_w.weight, mod.conv_w.bias)
-    if mod.mip in (8, 16) and c <= 512 and all(p is not None and p.dtype == torch.float32 for p in params):
+    # the width limit is the backward's (ly_coordatt_mlp_bwd): with grad disabled no backward follows and the forward takes any width
+    width_ok = (mod.mip in (8, 16) and c <= 512) or not torch.is_grad_enabled()
+    if width_ok and all(p is not None and p.dtype == torch.float32 for p in params):
         return CoordAttFn.apply(mod, x, *params)
     raise NotImplementedError(f"CoordAtt training is built for mip = max(8, c // 32) in (8, 16) and c <= 512 with float32 parameters (got mip={mod.mip}, "
                               f"c={c}): ly_coordatt_mlp_bwd has no instantiation for other widths, and there is no ATen fallback on the hot path")

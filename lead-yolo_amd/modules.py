@@ -13,6 +13,10 @@ nn.Conv2d / nn.BatchNorm2d / nn.Linear sub-modules are PARAMETER HOLDERS ONLY (t
 reference's key names and let `initialize_weights` / `fuse()` treat them as usual); their own
 forward is never called.  All arithmetic of the hot path runs in HIP kernels on NHWC (channels_last)
 activations.  There is no CPU path: calling forward without the GPU library raises.
+
+A module in train mode (`self.training`) runs its training node — the autograd.Function of grad.py — whether or not autograd records:
+under no_grad the node's forward issues the same launches and its context is dropped.  What a `forward` holds below that dispatch is
+the eval path.
 """
 import torch
 import torch.nn as nn
@@ -80,11 +84,6 @@ def _probe(x, shape):
     if SHAPE_PROBE and isinstance(x, torch.Tensor) and not x.is_cuda:
         return x.new_zeros(shape)
     return None
-
-
-def _grad_mode(mod):
-    """Training step: train-mode module called with autograd recording -> the autograd.Function path (grad.py)."""
-    return mod.training and torch.is_grad_enabled()
 
 
 _SIDE_STREAMS = {}
@@ -158,13 +157,11 @@ class Lazy:
         return parts[0] if len(parts) == 1 else torch.cat(parts, 1)
 
 
-def _run_pointwise(src, wp, n_out, e_scale, e_shift, act, out=None, ldo=None, **extra):
+def _run_pointwise(src, wp, n_out, e_scale, e_shift, act, out=None, ldo=None):
     """GEMM over a Lazy / tensor source -> NHWC tensor [n, n_out, h, w] (or into `out` rows)."""
     L = Lazy.of(src)
     n, c, h, w = L.shape
-    if extra.get("stats") is not None:
-        res, out_t, ldo = None, None, n_out                     # statistics pass: nothing is stored
-    elif out is None:
+    if out is None:
         res = ops.empty_nhwc(n, n_out, h, w, L.a0)
         out_t, ldo = res, n_out
     else:
@@ -173,7 +170,6 @@ def _run_pointwise(src, wp, n_out, e_scale, e_shift, act, out=None, ldo=None, **
               ldo=ldo, e_scale=e_scale, e_shift=e_shift, act=act, gather=ops.GATHER_UP2 if L.up else ops.GATHER_ROWS)
     if L.gate is not None:
         kw.update(pro=ops.PRO_GATE, g_h=L.gate[0], g_w=L.gate[1])
-    kw.update(extra)
     ops.gemm(**kw)
     return res
 
@@ -269,7 +265,7 @@ class MLPBlock(nn.Module):
             return pr
         if self.dim not in ops.MLP_WIDTHS:
             return self._forward_composed(x)
-        if _grad_mode(self):
+        if self.training:
             from . import grad
             bn = self.mlp[1]
             return grad.MlpBlockFn.apply(self, x, self.spatial_mixing.partial_conv3.weight, self.mlp[0].weight, bn.weight, bn.bias,
@@ -277,13 +273,7 @@ class MLPBlock(nn.Module):
         x = ops.nhwc(x)
         n, c, h, w = x.shape
         wp, w1, w2 = self._weights(ops.planes_of(x))
-        if self.training:
-            htp = (2 * c // 16 + 1) // 2 * 2
-            stats = ops.new_stats(16 * htp, x.device)
-            ops.mlpblock(x, None, n, h, w, c, wp, w1, w2, None, None, stats=stats)         # statistics pass (no store)
-            sc, sh = ops.bn_finalize(self.mlp[1], stats, 16 * htp, n * h * w, n=2 * c, pad_to=16 * htp)
-        else:
-            sc, sh = self._bn_eval()
+        sc, sh = self._bn_eval()
         y = ops.empty_nhwc(n, c, h, w, x)
         ops.mlpblock(x, y, n, h, w, c, wp, w1, w2, sc, sh)
         return y
@@ -359,8 +349,8 @@ class _PatchConv(nn.Module):
             odt = torch.float32 if want == torch.float32 else torch.bfloat16
             back = torch.float16 if want == torch.float16 else None
             if x.dtype != torch.uint8:
-                # a bf16 / fp16 image of a no-grad bf16 forward is gathered as it is (LY_GATHER_PATCH_NCHW_BF16 / _F16); everything else as fp32
-                half_img = x.dtype in (torch.bfloat16, torch.float16) and odt == torch.bfloat16 and not _grad_mode(self) and self.k == 4 and x.shape[3] % 4 == 0
+                # a bf16 / fp16 image of a bf16 forward outside train mode is gathered as it is (LY_GATHER_PATCH_NCHW_BF16 / _F16); everything else as fp32
+                half_img = x.dtype in (torch.bfloat16, torch.float16) and odt == torch.bfloat16 and not self.training and self.k == 4 and x.shape[3] % 4 == 0
                 if not half_img:
                     x = x.float()
                     ops.require_cuda(x, type(self).__name__, self)
@@ -377,7 +367,7 @@ class _PatchConv(nn.Module):
         planes = 2 if nchw else ops.planes_of(odt)       # the image gather contracts in bf16x3 (fp32 source) whatever the output dtype
         if not nchw and c % ops.vw_of(odt) != 0:
             raise NotImplementedError(f"{type(self).__name__}: {odt} patch gathers need channels % {ops.vw_of(odt)} == 0 (got {c})")
-        if _grad_mode(self) and isinstance(getattr(self, "norm", None), nn.BatchNorm2d):
+        if self.training and isinstance(getattr(self, "norm", None), nn.BatchNorm2d):
             from . import grad
             if nchw and (k != 4 or w % 4 != 0):
                 raise NotImplementedError("HIP patch embedding of an NCHW image needs patch_size 4 and W % 4 == 0")
@@ -396,15 +386,7 @@ class _PatchConv(nn.Module):
             xr = x.contiguous()                     # NCHW image
             kw = dict(M=n * ho * wo, H=ho, W=wo, K=16 * c, N=self.cout, a0=xr, lda0=0, k0=16 * c, wp=self._weights(True, planes),
                       ldo=self.cout, gather=ops.GATHER_PATCH_NCHW, Hin=h, Win=w, Cin=c, ks=4, pk=0, dtype=odt)
-        bn = getattr(self, "norm", None)
-        if self.training and isinstance(bn, nn.BatchNorm2d):
-            conv = getattr(self, self._conv_name)
-            bias = conv.bias.detach().float().contiguous() if conv.bias is not None else None
-            stats = ops.new_stats(self.cout, x.device)
-            ops.gemm(out=None, e_scale=None, e_shift=bias, stats=stats, **kw)                  # statistics pass
-            sc, sh = ops.bn_finalize(bn, stats, self.cout, n * ho * wo, bias=bias)
-        else:
-            sc, sh = self._affine_eval()
+        sc, sh = self._affine_eval()
         out = ops.empty_nhwc(n, self.cout, ho, wo, x, dtype=odt)
         ops.gemm(out=out, e_scale=sc, e_shift=sh, **kw)
         return out
@@ -481,15 +463,14 @@ class Conv(nn.Module):
             return None, (conv.bias.detach().float().contiguous() if conv.bias is not None else None)
         return self._prep_bn.get(key, build)
 
-    def _run(self, x, sc, sh, act, stats=None):
+    def _run(self, x, sc, sh, act):
         wp = self.weights(ops.planes_of(x.a0 if isinstance(x, Lazy) else x))
         if self.k == 1:
-            return _run_pointwise(x, wp, self.c2, sc, sh, act, stats=stats)
+            return _run_pointwise(x, wp, self.c2, sc, sh, act)
         xr, ld = ops.rows(x)
         n, c, h, w = xr.shape
-        out = None if stats is not None else ops.empty_nhwc(n, self.c2, h, w, xr)
-        ops.conv3x3(M=n * h * w, H=h, W=w, Cin=c, N=self.c2, x=xr, ldx=ld, wp=wp, out=out, ldo=self.c2, e_scale=sc, e_shift=sh, act=act,
-                    stats=stats)
+        out = ops.empty_nhwc(n, self.c2, h, w, xr)
+        ops.conv3x3(M=n * h * w, H=h, W=w, Cin=c, N=self.c2, x=xr, ldx=ld, wp=wp, out=out, ldo=self.c2, e_scale=sc, e_shift=sh, act=act)
         return out
 
     @_edge
@@ -510,7 +491,7 @@ class Conv(nn.Module):
                 raise NotImplementedError("HIP Conv with stride 2 is built for inference (eval mode) only")
             sc, sh = self.affine_eval()
             return self._run(x, sc, sh, act)[:, :, ::2, ::2].contiguous(memory_format=torch.channels_last)
-        if _grad_mode(self) and bn is not None:
+        if self.training and bn is not None:
             from . import grad
             x0, x1, up = x, None, False
             if isinstance(x, Lazy):
@@ -520,15 +501,7 @@ class Conv(nn.Module):
                     x0, x1, up = x.keep[0], (x.keep[1] if x.a1 is not None else None), x.up
             spec = grad.ConvSpec("pw" if self.k == 1 else "c3", self.c2, act, bn, True, up=up)
             return grad.conv_bn_act(spec, self.weights(ops.planes_of(x0)), x0, x1, self.conv.weight, self.conv.bias, bn)
-        if self.training and bn is not None:
-            L = Lazy.of(x)
-            n, _, h, w = L.shape
-            bias = self.conv.bias.detach().float().contiguous() if self.conv.bias is not None else None
-            stats = ops.new_stats(self.c2, L.a0.device)
-            self._run(x, None, bias, ACT_NONE, stats=stats)                                   # statistics pass
-            sc, sh = ops.bn_finalize(bn, stats, self.c2, n * h * w, bias=bias)
-        else:
-            sc, sh = self.affine_eval()
+        sc, sh = self.affine_eval()
         return self._run(x, sc, sh, act)
 
     def forward_fuse(self, x):
@@ -637,7 +610,7 @@ class RFCBAMConv(nn.Module):
         pr = _probe(x, (x.shape[0], self.o, (x.shape[2] + 2 * (k_ // 2) - k_) // s_ + 1, (x.shape[3] + 2 * (k_ // 2) - k_) // s_ + 1))
         if pr is not None:
             return pr
-        if _grad_mode(self):
+        if self.training:
             from . import grad
             return grad.rfcbam_train(self, x)
         xr, ld = ops.rows(x)
@@ -650,75 +623,38 @@ class RFCBAMConv(nn.Module):
         # are their own pass.  (The reference reads x for the pool, again for `generate`, and walks the 9x tensor ~13 times.)
         if k == 1:
             a1, b1, es, eb = P["a1"], P["b1"], P["es"], P["eb"]
-            if self.training:
-                # generate = per-channel scale g_c followed by BatchNorm over (n, h, w): its batch statistics follow
-                # from the per-channel moments of x:  mean = g*E[x],  E[a^2] = g^2 * E[x^2]
-                gwv = self.generate[0].weight.detach().float().view(c)
-                mom = ops.chan_moments(xr, ld, n * h * w, c)
-                gs, gb = ops.bn_batch_affine(self.generate[1], gwv * mom[:c], gwv * gwv * mom[c:], n * h * w)
-                a1, b1 = (gwv * gs).contiguous(), gb
             mm, part = ops.rfcbam_stats(xr, ld, n, h, w, c, 1, 1, a1=a1, b1=b1, gap=True)
             ca, rfa = ops.rfcbam_mid(part, h * w, wa, wb, self.se.ratio, mm, P["w18"])
-            kw = dict(M=n * h * w, H=h, W=w, K=c, N=self.o, a0=xr, lda0=ld, k0=c, wp=P["wp"], ldo=self.o, pro=ops.PRO_AFFINE_RELU_CA,
-                      p_scale=a1, p_shift=b1, p_ca=ca, rowscale=rfa)
-            if self.training:
-                bias = self.conv[0].bias.detach().float().contiguous()
-                stats = ops.new_stats(self.o, xr.device)
-                ops.gemm(out=None, e_scale=None, e_shift=bias, stats=stats, **kw)               # conv.1 BatchNorm statistics pass
-                es, eb = ops.bn_finalize(self.conv[1], stats, self.o, n * h * w, bias=bias)
             out = ops.empty_nhwc(n, self.o, h, w, xr)
-            ops.gemm(out=out, e_scale=es, e_shift=eb, act=ACT_RELU, **kw)
+            ops.gemm(M=n * h * w, H=h, W=w, K=c, N=self.o, a0=xr, lda0=ld, k0=c, wp=P["wp"], out=out, ldo=self.o, pro=ops.PRO_AFFINE_RELU_CA,
+                     p_scale=a1, p_shift=b1, p_ca=ca, rowscale=rfa, e_scale=es, e_shift=eb, act=ACT_RELU)
             return out
         ho, wo = (h + 2 - 3) // s + 1, (w + 2 - 3) // s + 1
-        if RF3M and not self.training and ops.rf3m_ok(xr, c, self.o, s, n, ho, wo):
+        if RF3M and ops.rf3m_ok(xr, c, self.o, s, n, ho, wo):
             return self._forward3_m(xr, ld, n, c, h, w, ho, wo, s, P, wa, wb)
-        # (fp32 storage with more than 128 output channels: the lane = pixel kernels measure faster — layer 20 at bs=64: 215 vs 289 us —
+        # (inference in fp32 storage with more than 128 output channels: the lane = pixel kernels measure faster — layer 20 at bs=64: 215 vs 289 us —
         # the two-plane operand tile of the lane = channel kernel leaves one block per CU there)
         if ops.rf3c_ok(c, s) and RF3C and not (xr.dtype == torch.float32 and self.o > 128):
             return self._forward3_c(xr, ld, n, c, h, w, ho, wo, s, P, wa, wb)
         th, tw = ops.pick_tile(ho, wo)
-        wq_stats, wq_main, es, eb = P["wq_stats"], P["wq_main"], P["es"], P["eb"]
-        if self.training:
-            gw = self.generate[0].weight
-            s1, s2, cnt = ops.rfcbam_generate_stats(xr, ld, n, h, w, c, s, gw)                # generate.1 batch statistics
-            gs, gb = ops.bn_batch_affine(self.generate[1], s1, s2, cnt)
-            wq_stats = pack.rfcbam_gen_weights(gw, gs, gb, 32, False)
-            wq_main = pack.rfcbam_gen_weights(gw, gs, gb, 16, True)
         part = ops.colsum(xr, ld, n, h * w, c)                                                 # k = 3: pooling partials as their own pass
-        mm = ops.rfcbam_stats(xr, ld, n, h, w, c, 3, s, wg=wq_stats, th=th, tw=tw)
+        mm = ops.rfcbam_stats(xr, ld, n, h, w, c, 3, s, wg=P["wq_stats"], th=th, tw=tw)
         ca, rfa = ops.rfcbam_mid(part, h * w, wa, wb, self.se.ratio, mm, P["w18"])
-        kw = dict(n=n, h=h, w=w, c=c, ho=ho, wo=wo, N=self.o, s=s, th=th, tw=tw, x=xr, ldx=ld, wg=wq_main, ca=ca, rfa=rfa, wp=P["wp"],
-                  ldo=self.o)
-        if self.training:
-            bias = self.conv[0].bias.detach().float().contiguous()
-            stats = ops.new_stats(self.o, xr.device)
-            ops.rfcbam3(out=None, e_scale=torch.ones_like(bias), e_shift=bias, stats=stats, **kw)   # conv.1 statistics pass
-            es, eb = ops.bn_finalize(self.conv[1], stats, self.o, n * ho * wo, bias=bias)
         out = ops.empty_nhwc(n, self.o, ho, wo, xr)
-        ops.rfcbam3(out=out, e_scale=es, e_shift=eb, **kw)
+        ops.rfcbam3(n=n, h=h, w=w, c=c, ho=ho, wo=wo, N=self.o, s=s, th=th, tw=tw, x=xr, ldx=ld, wg=P["wq_main"], ca=ca, rfa=rfa, wp=P["wp"],
+                    e_scale=P["es"], e_shift=P["eb"], out=out, ldo=self.o)
         return out
 
 
     def _forward3_c(self, xr, ld, n, c, h, w, ho, wo, s, P, wa, wb):
-        """k = 3 on the lane = channel kernels (csrc/ly_rf3c.hip), three launches, x read twice: (1) [max, mean] map + SE pooling partials,
+        """k = 3, inference, on the lane = channel kernels (csrc/ly_rf3c.hip), three launches, x read twice: (1) [max, mean] map + SE pooling partials,
         (2) SE linears + get_weight's conv on the small maps, (3) regenerate + contraction."""
         th, tw = ops.pick_tile_c(ho, wo, s)
-        wq, es, eb = P["wq_c"], P["es"], P["eb"]
-        if self.training:
-            gw = self.generate[0].weight
-            s1, s2, cnt = ops.rfcbam_generate_stats(xr, ld, n, h, w, c, s, gw)                # generate.1 batch statistics
-            gs, gb = ops.bn_batch_affine(self.generate[1], s1, s2, cnt)
-            wq = pack.rfcbam_gen_weights_c(gw, gs, gb)
-        mm, part = ops.rf3c_stats(xr, ld, n, h, w, c, s, wq, th, tw)
+        mm, part = ops.rf3c_stats(xr, ld, n, h, w, c, s, P["wq_c"], th, tw)
         ca, rfa = ops.rfcbam_mid(part, h * w, wa, wb, self.se.ratio, mm, P["w18"])
-        kw = dict(n=n, h=h, w=w, c=c, ho=ho, wo=wo, N=self.o, s=s, th=th, tw=tw, x=xr, ldx=ld, wq=wq, ca=ca, rfa=rfa, wp=P["wp_c"], ldo=self.o)
-        if self.training:
-            bias = self.conv[0].bias.detach().float().contiguous()
-            stats = ops.new_stats(self.o, xr.device)
-            ops.rf3c_fwd(out=None, e_scale=ops.ones_f32(bias.numel(), bias.device), e_shift=bias, stats=stats, **kw)   # conv.1 statistics pass
-            es, eb = ops.bn_finalize(self.conv[1], stats, self.o, n * ho * wo, bias=bias)
         out = ops.empty_nhwc(n, self.o, ho, wo, xr)
-        ops.rf3c_fwd(out=out, e_scale=es, e_shift=eb, **kw)
+        ops.rf3c_fwd(n=n, h=h, w=w, c=c, ho=ho, wo=wo, N=self.o, s=s, th=th, tw=tw, x=xr, ldx=ld, wq=P["wq_c"], ca=ca, rfa=rfa, wp=P["wp_c"],
+                     e_scale=P["es"], e_shift=P["eb"], out=out, ldo=self.o)
         return out
 
 
@@ -800,12 +736,7 @@ class CoordAtt(nn.Module):
     def attention(self, xr, ld, n, h, w, c):
         w1raw, b1raw, wh, bh, ww, bw = self._weights()
         pool = ops.pool_hw(xr, ld, n, h, w, c)
-        if self.training:
-            st = ops.coordatt_conv1_stats(pool, n * (h + w), c, self.mip, w1raw, b1raw).float()       # bn1 batch statistics (double accumulators)
-            sc, sh = ops.bn_batch_affine(self.bn1, st[:self.mip], st[self.mip:], n * (h + w))
-            w1, b1 = (w1raw * sc.view(-1, 1)).contiguous(), (b1raw * sc + sh).contiguous()
-        else:
-            w1, b1 = self._conv1_eval()
+        w1, b1 = self._conv1_eval()
         return ops.coordatt_mlp(pool, n, h, w, c, self.mip, w1, b1, wh, bh, ww, bw)
 
     @_edge
@@ -813,7 +744,7 @@ class CoordAtt(nn.Module):
         pr = _probe(x, x.shape)
         if pr is not None:
             return pr
-        if _grad_mode(self):
+        if self.training:
             from . import grad
             return grad.coordatt_train(self, x)
         xr, ld = ops.rows(x)
@@ -833,7 +764,7 @@ class CA_Bottleneck(nn.Module):
 
     def forward_lazy(self, x):
         """Returns a Lazy (gated, un-materialised) output when there is no residual, else a tensor."""
-        if _grad_mode(self):
+        if self.training:
             xin = x.materialize() if isinstance(x, Lazy) else x
             y = self.ca(self.cv2(self.cv1(xin)))
             return xin + y if self.add else y
@@ -928,7 +859,7 @@ class C3_CA(nn.Module):
         c_ = self.c_
         if _act_code(self.cv1.act) != _act_code(self.cv2.act):
             raise NotImplementedError("C3_CA: cv1 and cv2 must share one activation")
-        if _grad_mode(self):
+        if self.training:
             a, b = self._cv12_train(x)
             for blk in self.m:
                 a = blk.forward_lazy(a)
@@ -937,15 +868,7 @@ class C3_CA(nn.Module):
             tb, ldb = ops.rows(b)
             return self.cv3(Lazy((n_, ca_ + b.shape[1], h_, w_), ta, lda, ca_, a1=tb, lda1=ldb, keep=(ta, tb)))
         wp = self._weights12(ops.planes_of(src.a0))
-        b1, b2 = getattr(self.cv1, "bn", None), getattr(self.cv2, "bn", None)
-        if self.training and b1 is not None and b2 is not None:
-            stats = ops.new_stats(2 * c_, src.a0.device)
-            _run_pointwise(src, wp, 2 * c_, None, None, ACT_NONE, stats=stats)                  # statistics pass, both halves
-            sa, ta = ops.bn_finalize(b1, stats, 2 * c_, n * h * w, n=c_, c_off=0)
-            sb, tb = ops.bn_finalize(b2, stats, 2 * c_, n * h * w, n=c_, c_off=c_)
-            sc, sh = torch.cat((sa, sb)).contiguous(), torch.cat((ta, tb)).contiguous()
-        else:
-            sc, sh = self._affine12_eval()
+        sc, sh = self._affine12_eval()
         ycat = ops.empty_nhwc(n, 2 * c_, h, w, src.a0)
         _run_pointwise(src, wp, 2 * c_, sc, sh, _act_code(self.cv1.act), out=ycat, ldo=2 * c_)
         cur = Lazy((n, c_, h, w), ycat, 2 * c_, c_, keep=(ycat,))
@@ -974,7 +897,7 @@ class SPPF(nn.Module):
             return y.new_zeros((y.shape[0], self.cv2.c2, y.shape[2], y.shape[3]))
         n, c_, h, w = y.shape
         k = self.m.kernel_size
-        if _grad_mode(self):
+        if self.training:
             from . import grad
             return self.cv2(grad.SppfPool.apply(y, k))
         if ops.sppf_pool_fits(h, w):
@@ -1100,7 +1023,7 @@ class Detect(nn.Module):
             return self._fwd(x)
 
     def _fwd(self, x):
-        if _grad_mode(self):
+        if self.training and torch.is_grad_enabled():      # the loss follows: raw fp32 maps through grad.detect_head
             from . import grad
             for i in range(self.nl):
                 t = x[i].materialize() if isinstance(x[i], Lazy) else x[i]
@@ -1167,9 +1090,12 @@ class Detect(nn.Module):
             p = ext["p"][i] if ext is not None else torch.empty((st["bs"], self.na, ny, nx, self.no), dtype=torch.float32, device=st["device"])
             fused = self._fused_level_input(i, xi)
             if fused is not None:                           # head convolution + decode in one launch (csrc/ly_detect.hip)
-                wp, b = self._packed_nat(i, ops.planes_of(xi))
+                # train mode (raw maps only, grad disabled): the weight image grad.DetectHeadFn contracts with, so that the maps are bit
+                # for bit those of the recording forward (the natural-k image sums the products of a k-step in another order)
+                nat = not self.training
+                wp, b = self._packed_nat(i, ops.planes_of(xi)) if nat else self._packed(i, ops.planes_of(xi))
                 ops.detect_level(fused[0], fused[1], st["bs"], ny, nx, self.m[i].in_channels, wp, b, self.na, self.no, self.anchors[i],
-                                 self._strides()[i], p, st["z"], st["zrows"], st["offs"][i])
+                                 self._strides()[i], p, st["z"], st["zrows"], st["offs"][i], nat=nat)
             else:
                 buf, ldo = self._head(i, xi)
                 ops.detect_tail(buf, ldo, st["bs"], ny, nx, self.na, self.no, self.anchors[i], self._strides()[i], p, st["z"], st["zrows"],

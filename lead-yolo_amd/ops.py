@@ -871,7 +871,7 @@ def zeros_f32(numel, device):
     return torch.zeros(numel, dtype=torch.float32, device=device)
 
 
-def bn_finalize(bn, stats, nch, count, n=None, c_off=0, bias=None, pad_to=0, want_stats=False, into=None):
+def bn_finalize(bn, stats, nch, count, n=None, c_off=0, pad_to=0, want_stats=False, into=None):
     """Train-mode BatchNorm2d from the striped sums of a statistics pass, ONE launch (ly_bn_finalize): returns
     (scale, shift) of y = x*scale + shift [+ (mean, invstd)], updates running_mean/var/num_batches_tracked in place.
     into = (scale, shift, mean, invstd): contiguous fp32 [n] destinations (slices of a wider vector: two BatchNorms over one stacked output)."""
@@ -899,7 +899,7 @@ def bn_finalize(bn, stats, nch, count, n=None, c_off=0, bias=None, pad_to=0, wan
         pack.touch()                     # running statistics are written by the kernel: eval-mode folded caches must refresh
     if stats.dtype not in (torch.float32, torch.float64):
         raise TypeError("bn_finalize: statistics must be float32 or float64")
-    capi.check(capi.lib().ly_bn_finalize(_p(stats), int(stats.dtype == torch.float64), stats.shape[0], nch, c_off, n, float(count), _p(bn.weight), _p(bn.bias), _p(bias), float(bn.eps),
+    capi.check(capi.lib().ly_bn_finalize(_p(stats), int(stats.dtype == torch.float64), stats.shape[0], nch, c_off, n, float(count), _p(bn.weight), _p(bn.bias), None, float(bn.eps),
                                          float(bn.momentum or 0.0), _p(bn.running_mean if track else None), _p(bn.running_var if track else None),
                                          _p(bn.num_batches_tracked if track else None), _p(scale), _p(shift), _p(mean), _p(invstd),
                                          capi.stream_ptr()), "ly_bn_finalize")
@@ -1022,38 +1022,6 @@ def coordatt_conv1_stats(pool, positions, c, mip, w1, b1):
     return st
 
 
-def bn_batch_affine(bn, s1, s2, count):
-    """Train-mode BatchNorm from per-channel sums: returns (scale, shift) of y = x*scale + shift with the
-    BATCH statistics (biased variance), and updates running_mean / running_var (unbiased, momentum) and
-    num_batches_tracked in place exactly as nn.BatchNorm2d does.  Device tensors only, no host sync."""
-    return bn_batch_stats(bn, s1, s2, count)[:2]
-
-
-_TRIU = None
-
-
-def rfcbam_generate_stats(x, ldx, n, h, w, c, s, gen_w):
-    """Batch statistics of the k=3 `generate` BatchNorm input: returns (sum a, sum a^2) per generate channel
-    (c*9 + t) and the sample count, from the per-channel tap moments (see ly_rfcbam_tap_moments)."""
-    global _TRIU
-    mom = torch.zeros(54, c, dtype=torch.float64, device=x.device)
-    with _Timed(f"ly_rfcbam_tap_moments_kernel<{_tname(x)}>", 108.0 * n * h * w * c / (s * s), x.element_size() * n * h * w * c):
-        capi.check(capi.lib().ly_rfcbam_tap_moments(_p(x), ldx, n, h, w, c, s, _p(mom), capi.dtype_code(x), capi.stream_ptr()), "ly_rfcbam_tap_moments")
-    mom = mom.float()
-    if _TRIU is None or _TRIU[0].device != x.device:
-        iu = torch.triu_indices(9, 9, device=x.device)
-        _TRIU = (iu[0], iu[1])
-    m1 = mom[:9].t()                                            # [c, 9]
-    M = torch.zeros(c, 9, 9, dtype=torch.float32, device=x.device)
-    M[:, _TRIU[0], _TRIU[1]] = mom[9:].t()
-    M = M + M.transpose(1, 2) - torch.diag_embed(torch.diagonal(M, dim1=1, dim2=2))
-    wv = gen_w.detach().float().view(c, 9, 9)                  # [c, t, u]
-    s1 = torch.einsum("ctu,cu->ct", wv, m1)
-    s2 = torch.einsum("ctu,cuv,ctv->ct", wv, M, wv)
-    ho, wo = (h + 2 - 3) // s + 1, (w + 2 - 3) // s + 1
-    return s1.reshape(-1), s2.reshape(-1), n * ho * wo
-
-
 def rfcbam_gen_prepare(x, ldx, n, h, w, c, k, s, gen_w, bn):
     """Train-mode `generate` BatchNorm of RFCBAMConv in two launches: the moment kernel over x, then ly_rfcbam_gen_prepare (batch
     statistics, running-stat update, scale / shift in both index orders and the folded weights in the kernels' LDS orders).
@@ -1090,22 +1058,6 @@ def rfcbam_gen_prepare(x, ldx, n, h, w, c, k, s, gen_w, bn):
 
 
 # ---- backward building blocks (training step) --------------------------------------------------------
-def bn_batch_stats(bn, s1, s2, count):
-    """As bn_batch_affine, additionally returning the batch mean and 1/sqrt(var + eps) the backward needs."""
-    with torch.no_grad():
-        mean = s1 / count
-        var = (s2 / count - mean * mean).clamp_(min=0.0)
-        invstd = torch.rsqrt(var + bn.eps)
-        scale = bn.weight.detach().float() * invstd
-        shift = bn.bias.detach().float() - mean * scale
-        if bn.track_running_stats and bn.running_mean is not None:
-            mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked + 1)
-            bn.running_mean.mul_(1.0 - mom).add_(mean, alpha=mom)
-            bn.running_var.mul_(1.0 - mom).add_(var * (count / max(count - 1, 1)), alpha=mom)
-            bn.num_batches_tracked += 1
-    return scale.contiguous(), shift.contiguous(), mean, invstd
-
-
 def bnact_fwd(u, ldu, rows, c, a, b, act, y, ldy):
     with _Timed(f"ly_bnact_fwd_kernel<{_tname(u)}, {act}>", 4.0 * rows * c, 2.0 * u.element_size() * rows * c):
         capi.check(capi.lib().ly_bnact_fwd(_p(u), ldu, rows, c, _p(a), _p(b), act, _p(y), ldy, capi.dtype_code(u), capi.stream_ptr()), "ly_bnact_fwd")

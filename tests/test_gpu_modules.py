@@ -257,6 +257,94 @@ def test_whole_model_train_forward_golden(scale):
         assert err.max() <= 5e-3 + 5e-3 * np.abs(want).max(), (scale, i, err.max())
 
 
+def _running(sd):
+    return {k: v for k, v in sd.items() if k.endswith(("running_mean", "running_var", "num_batches_tracked"))}
+
+
+def _same_bits(a, b, what):
+    assert a.dtype == b.dtype and a.shape == b.shape, (what, a.dtype, b.dtype, a.shape, b.shape)
+    if not torch.equal(a, b):
+        d = (a.double() - b.double()).abs()
+        raise AssertionError(f"{what}: {int((d > 0).sum())} / {d.numel()} elements differ between the no-grad and the grad-enabled run, max {float(d.max()):.3e}")
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("name", TRAIN_MODULES)
+def test_module_train_forward_same_bits_with_and_without_grad(name, dt):
+    """a train-mode module runs its training node whether or not autograd records: the output and the running-statistics updates of a
+    no_grad call are bit for bit those of a call that records (bf16: storage and autocast as in tests/test_gpu_bf16.py)"""
+    meta, _ = G.load(name)
+    st = G.state_for(meta)
+    x = synth.synth_input(meta["in_shape"], meta["seed"] + 1).to(_dev())
+    if dt == torch.bfloat16 and x.shape[1] != 3:          # (an image stays fp32: the patch gather converts)
+        x = x.to(dt)
+    res = []
+    for record in (False, True):
+        m = _bn_eps(_load(_ctor(meta["kind"])(*meta["ctor"]), st)).to(_dev()).train()
+        xi = x.clone().requires_grad_(record)
+        with torch.set_grad_enabled(record), torch.autocast("cuda", dtype=torch.bfloat16, enabled=dt == torch.bfloat16):
+            y = m(xi)
+        assert y.requires_grad == record and y.dtype == dt
+        res.append((y.detach(), _running(m.state_dict())))
+    (y0, r0), (y1, r1) = res
+    _same_bits(y0, y1, name)
+    assert r0.keys() == r1.keys() and len(r0) > 0
+    for k in r0:
+        _same_bits(r0[k], r1[k], f"{name} {k}")
+
+
+def test_whole_model_train_forward_same_bits_with_and_without_grad():
+    """the same for the whole detector (lead-yolo-n at the golden's input size), every returned level"""
+    import lead_yolo_amd as L
+    meta, _ = G.load("model_n")
+    _, pa = G.load("parse_n")
+    st = G.state_for(meta, {"model.23.anchors": G.t(pa["anchors"])})
+    hw = meta["hw"]
+    x = (synth.synth_images(2, max(hw), meta["seed"] + 1)[:, :, :hw[0], :hw[1]].float() / 255).to(_dev())
+    res = []
+    for record in (False, True):
+        m = L.Model(_cfg("n"))
+        m.load_state_dict(st)
+        m = m.to(_dev()).train()
+        with torch.set_grad_enabled(record):
+            outs = m(x.clone().requires_grad_(record))
+        res.append(([o.detach() for o in outs], _running(m.state_dict())))
+    (o0, r0), (o1, r1) = res
+    assert len(o0) == len(o1) == 3
+    for i, (a, b) in enumerate(zip(o0, o1)):
+        _same_bits(a, b, f"model_n p{i}")
+    assert r0.keys() == r1.keys() and len(r0) > 0
+    for k in r0:
+        _same_bits(r0[k], r1[k], f"model_n {k}")
+
+
+def test_coordatt_width_without_backward_runs_train_mode_under_no_grad():
+    """CoordAtt(384, 384): mip = 12, a width ly_coordatt_mlp_bwd is not instantiated for.  With frozen parameters it goes into train mode;
+    under no_grad its forward (bn1 on batch statistics) matches the oracle, with grad enabled it is refused as before"""
+    import lead_yolo_amd as L
+    torch.manual_seed(0)
+    m = L.CoordAtt(384, 384)
+    assert m.mip == 12
+    st = synth.synth_state(synth.shapes_of(m.state_dict()), 9384)
+    _bn_eps(_load(m, st))
+    for p in m.parameters():
+        p.requires_grad_(False)
+    x = synth.synth_input((2, 384, 8, 12), 415)
+    so = copy.deepcopy(st)
+    with torch.no_grad():
+        want = OF.coord_att(so, "", x, True)
+    m = m.to(_dev()).train()
+    with torch.no_grad():
+        got = m(x.to(_dev()))
+    _cmp(got, want, "CoordAtt(384) train, no_grad")
+    sd = m.state_dict()
+    for k in ("bn1.running_mean", "bn1.running_var"):
+        _cmp(sd[k], so[k], "CoordAtt(384) " + k)
+    assert int(sd["bn1.num_batches_tracked"]) == 1
+    with pytest.raises(NotImplementedError, match="CoordAtt training is built for mip"):
+        m(x.to(_dev()).requires_grad_(True))
+
+
 def test_graphed_forward_matches_eager():
     """serving mode: the forward captured into a hipGraph (with the SE / early-Detect branches forked onto the auxiliary
     stream) must return exactly what the eager single-stream forward returns, also after new input is copied in"""

@@ -135,3 +135,10 @@ def test_two_consumer_layers_follow_the_routing_table(scale):
             readers.setdefault(mod.i - 1 if j == -1 else j, []).append(mod.i)
     assert sorted(m._two_consumer_layers()) == sorted(j for j, r in readers.items() if len(r) == 2 and j >= 0) == [3, 5, 9, 13, 16, 19]
     assert all(j in m.save or readers[j] == [j + 1] or (j + 1) in readers[j] for j in m._two_consumer_layers())
+
+
+def test_host_arithmetic_batchnorm_helpers_are_gone():
+    """train mode has one forward, the training node's (kernels take and finalize the batch statistics): the torch-arithmetic helpers
+    of the former second forward must not come back"""
+    for name in ("bn_batch_affine", "bn_batch_stats", "rfcbam_generate_stats"):
+        assert not hasattr(L.ops, name), name
