@@ -13,6 +13,7 @@ Scheme for every conv -> BN -> act unit (v = a*u + b with the BATCH statistics, 
     4. dgrad: forward kernel on du with transposed weights;  wgrad: ly_wgrad (pixel contraction)
 Only [C]-sized vectors are handled with torch ops (coefficients of step 3, parameter-gradient reshapes).
 """
+import collections
 import ctypes
 
 import os
@@ -301,15 +302,6 @@ def conv_dgrad(spec, du, weight, x0, x1, need0, need1, slots=(None, None)):
         g = torch.empty((m, k * k * c), dtype=du.dtype, device=du.device)
         ops.gemm(M=m, H=ho, W=wo, K=co, N=k * k * c, a0=du, lda0=co, k0=co, wp=wt, out=g, ldo=k * k * c)
         return ops.unpatch(g, n, ho, wo, c, k, h, w), None
-
-
-def _pad_cols(w2d, k):
-    """[R, k0] -> [R, k] zero padded on the right (k >= k0)."""
-    if w2d.shape[1] == k:
-        return w2d
-    out = torch.zeros(w2d.shape[0], k, dtype=w2d.dtype, device=w2d.device)
-    out[:, :w2d.shape[1]] = w2d
-    return out
 
 
 class ConvBnAct(torch.autograd.Function):
@@ -629,24 +621,16 @@ class DetectHeadFn(torch.autograd.Function):
             vw = ops.vw_of(t0)
             cq = (co + vw - 1) // vw * vw
             dp = dp.float().contiguous()
-            tb = ops.grad_target(b_param)
-            tb = tb if tb is not None and tb.is_contiguous() and tb.numel() == co else None
-            defer = tb is not None and ops.small_grads_ok()       # float64 scratch, rounded into the sink when the backward pass ends
-            fresh64 = tb is None and ops.DETERMINISTIC_SMALL_GRADS      # no sink: float64 scratch, rounded right away (returned to autograd)
-            dbias = ops.small_grad_scratch(tb, b_param) if defer else tb if tb is not None else \
-                ops.zeros_f64(co, dp.device) if fresh64 else torch.zeros(co, dtype=torch.float32, device=dp.device)
+            gb = ops.SmallGrad(b_param, co)
             du = torch.empty((bs, ny, nx, cq), dtype=t0.dtype, device=dp.device)
-            ops.detect_head_bwd(dp, bs, ny, nx, na, no, du, cq, dbias)
-            if fresh64:
-                dbias = ops.f64_round([dbias], [(co,)])[0]
-            if tb is not None and not defer:
-                ops.grad_done(b_param)
+            ops.detect_head_bwd(dp, bs, ny, nx, na, no, du, cq, gb.buf)
+            dbias = gb.finish()
             du_d = du.permute(0, 3, 1, 2)
             dw = conv_wgrad(ctx.spec, du_d, x, None, w_param) if need[4] else None
             dx = None
             if need[3]:
                 dx, _ = conv_dgrad(ConvSpec("pw", cq), du_d, weight, x, None, True, False, ctx.slots)
-        return None, None, None, dx, dw, (None if tb is not None else dbias)
+        return None, None, None, dx, dw, dbias
 
 
 def detect_head(det, i, wp, x, weight, bias):
@@ -977,12 +961,8 @@ def _lib():
     return capi
 
 
-DEBUG_TAP = None        # tools/: callable(name, tensor) observing backward intermediates
-
-
-def _tap(name, t):
-    if DEBUG_TAP is not None:
-        DEBUG_TAP(name, t)
+# what RfcbamFn.forward saves, in the order of its save_for_backward: unpacked once per backward, read by the route and by the shared stages
+_RfSaved = collections.namedtuple("_RfSaved", "xr ca gen_w getw conv_w bias ag bg gmean_tc ginv_tc es t omean oinv mm rfa se_part u")
 
 
 class RfcbamFn(torch.autograd.Function):
@@ -1004,22 +984,15 @@ class RfcbamFn(torch.autograd.Function):
         if gen_w.dtype != torch.float32:
             raise NotImplementedError("RFCBAMConv training needs float32 parameters (train under autocast, fp32 master weights)")
         G = ops.rfcbam_gen_prepare(xr, ld, n, h, w, c, k, s, gen_w, mod.generate[1])          # generate BatchNorm: moments + ONE launch
-        gs, gb, gmean, ginv = G["gs"], G["gb"], G["gmean"], G["ginv"]
+        ctx.rc = None
+        # every branch: ca, rfa, mm, se_part and its contraction (called below: an identity scale is made after the accumulators, as ever)
         if k == 1:
-            a1 = G["a1"]
+            a1, gb = G["a1"], G["gb"]
             mm = ops.rfcbam_stats(xr, ld, n, h, w, c, 1, 1, a1=a1, b1=gb)
             rfa = ops.rfa_map(mm, P["w18"])
             kw = dict(M=n * h * w, H=h, W=w, K=c, N=o, a0=xr, lda0=ld, k0=c, wp=P["wp"], ldo=o, pro=ops.PRO_AFFINE_RELU_CA,
                       p_scale=a1, p_shift=gb, p_ca=ca, rowscale=rfa)
-            # ONE contraction: statistics and the pre-BN value u (bias included) in the same launch; y = relu(es*u + t) is an elementwise
-            # pass and u is kept for the backward (was: statistics pass + main pass + a recompute in backward)
-            stats = ops.new_stats(o, xr.device)
-            u = ops.empty_nhwc(n, o, h, w, xr)
-            ops.gemm(out=u, e_scale=None, e_shift=bias, stats=stats, **kw)
-            es, t, omean, oinv = ops.bn_finalize(mod.conv[1], stats, o, n * h * w, want_stats=True)
-            out = torch.empty_like(u)
-            ops.bnact_fwd(u, o, n * h * w, o, es, t, ACT_RELU, out, o)
-            ctx.fwd = dict(kw=kw)
+            contract = lambda **io: ops.gemm(e_scale=None, **kw, **io)
         elif rc:
             # three launches, x read twice: statistics + SE pooling partials | SE linears + get_weight conv | regenerate + contraction.  The RAW
             # generate image (u = w.x, v = a*u + b) is what the backward re-evaluates bit for bit
@@ -1027,29 +1000,22 @@ class RfcbamFn(torch.autograd.Function):
             mm, se_part = ops.rf3c_stats(xr, ld, n, h, w, c, s, G["wq_c"], th, tw, raw=True)
             ca, rfa = ops.rfcbam_mid(se_part, h * w, se_wa.detach(), se_wb.detach(), se_wa.shape[0], mm, P["w18"])
             kw = dict(n=n, h=h, w=w, c=c, ho=ho, wo=wo, N=o, s=s, th=th, tw=tw, x=xr, ldx=ld, wq=G["wq_c"], ca=ca, rfa=rfa, wp=P["wp_c"], ldo=o, raw=True)
-            stats = ops.new_stats(o, xr.device)
-            u = ops.empty_nhwc(n, o, ho, wo, xr)
-            ops.rf3c_fwd(out=u, e_scale=ops.ones_f32(bias.numel(), bias.device), e_shift=bias, stats=stats, **kw)
-            es, t, omean, oinv = ops.bn_finalize(mod.conv[1], stats, o, n * ho * wo, want_stats=True)
-            out = torch.empty_like(u)
-            ops.bnact_fwd(u, o, n * ho * wo, o, es, t, ACT_RELU, out, o)
-            ctx.fwd = dict(kw=kw)
+            contract = lambda **io: ops.rf3c_fwd(e_scale=ops.ones_f32(bias.numel(), bias.device), **kw, **io)
             ctx.rc = dict(th=th, tw=tw, wq=G["wq_c"])
         else:
             th, tw = ops.pick_tile(ho, wo)
-            wq_stats, wq_main = G["wq_stats"], G["wq_main"]
-            mm = ops.rfcbam_stats(xr, ld, n, h, w, c, 3, s, wg=wq_stats, th=th, tw=tw)
+            mm = ops.rfcbam_stats(xr, ld, n, h, w, c, 3, s, wg=G["wq_stats"], th=th, tw=tw)
             rfa = ops.rfa_map(mm, P["w18"])
-            kw = dict(n=n, h=h, w=w, c=c, ho=ho, wo=wo, N=o, s=s, th=th, tw=tw, x=xr, ldx=ld, wg=wq_main, ca=ca, rfa=rfa, wp=P["wp"], ldo=o)
-            stats = ops.new_stats(o, xr.device)
-            u = ops.empty_nhwc(n, o, ho, wo, xr)
-            ops.rfcbam3(out=u, e_scale=torch.ones_like(bias), e_shift=bias, stats=stats, **kw)      # one contraction (see k = 1)
-            es, t, omean, oinv = ops.bn_finalize(mod.conv[1], stats, o, n * ho * wo, want_stats=True)
-            out = torch.empty_like(u)
-            ops.bnact_fwd(u, o, n * ho * wo, o, es, t, ACT_RELU, out, o)
-            ctx.fwd = dict(kw=kw)
-        if not rc:
-            ctx.rc = None
+            kw = dict(n=n, h=h, w=w, c=c, ho=ho, wo=wo, N=o, s=s, th=th, tw=tw, x=xr, ldx=ld, wg=G["wq_main"], ca=ca, rfa=rfa, wp=P["wp"], ldo=o)
+            contract = lambda **io: ops.rfcbam3(e_scale=torch.ones_like(bias), **kw, **io)
+        # ONE contraction: statistics and the pre-BN value u (bias included) in the same launch; y = relu(es*u + t) is an elementwise
+        # pass and u is kept for the backward (was: statistics pass + main pass + a recompute in backward)
+        stats = ops.new_stats(o, xr.device)
+        u = ops.empty_nhwc(n, o, ho, wo, xr)
+        contract(out=u, e_shift=bias, stats=stats)
+        es, t, omean, oinv = ops.bn_finalize(mod.conv[1], stats, o, n * ho * wo, want_stats=True)
+        out = torch.empty_like(u)
+        ops.bnact_fwd(u, o, n * ho * wo, o, es, t, ACT_RELU, out, o)
         ctx.geom = (n, c, h, w, k, s, o, ho, wo, ld)
         ctx.conv_w_param = conv_w
         ctx.se_params = (se_wa, se_wb)
@@ -1063,149 +1029,177 @@ class RfcbamFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        xr, ca, gen_w, getw, conv_w, bias, ag, bg, gmean_tc, ginv_tc, es, t, omean, oinv, mm, rfa, se_part, u = ctx.saved_tensors
+        sv = _RfSaved(*ctx.saved_tensors)
+        xr = sv.xr
         n, c, h, w, k, s, o, ho, wo, ld = ctx.geom
-        kk = k * k
-        mo = n * ho * wo
-        dev = xr.device
-        L = _lib()
-        st = L.stream_ptr()
-        p = L.ptr
         with torch.no_grad():
             dt = xr.dtype
-            pl = ops.planes_of(xr)
-            code = L.dtype_code(xr)
             dy = _rows_dense(dy if dy.dtype == dt else dy.to(dt))
             # 1-2. output conv: the pre-BN value u (bias included) was kept by the forward; BN + ReLU backward (du is written over a copy
             # of u: saved tensors must stay intact for a second backward through the graph)
-            _tap("rf.dy", dy); _tap("rf.u", u)
-            du, dgo, dbo = affine_backward(dy, u, es, t, ACT_RELU, omean, oinv, True, inplace=False, gamma=ctx.out_bn_params[0],
+            du, dgo, dbo = affine_backward(dy, sv.u, sv.es, sv.t, ACT_RELU, sv.omean, sv.oinv, True, inplace=False, gamma=ctx.out_bn_params[0],
                                            beta=ctx.out_bn_params[1])       # (straight into the sink when one holds them: returns None, None)
-            _tap("rf.du", du)
             # (o = 256 — layer 20 — measured SLOWER on the recompute passes than on the streamed 9x tensors: 1.08 vs 0.73 ms of kernels at bs = 64;
             # layer 17, o = 128: 0.95 vs 1.47 ms.  The wider layer stays on the first-generation backward.)
-            if ctx.rc is not None and dt == torch.bfloat16 and s == 2 and o in RC_BWD_WIDTHS and RC_BWD:
-                return RfcbamFn._backward_rc(ctx, du, dgo, dbo)
-            if k == 1 and RF1_BWD and c % ops.vw_of(xr) == 0 and c // ops.vw_of(xr) <= 64 and ld % ops.vw_of(xr) == 0:
-                return RfcbamFn._backward_k1(ctx, du, dgo, dbo)
-            # 3. dcd [mo][t][c]
-            # Wc^T with rows (t, c): conv.0.weight [o, c, kh, kw] read in place
-            dcd = torch.empty((mo, kk * c), dtype=dt, device=dev)
-            wct = pack.packed(pack.Src(ctx.conv_w_param, kk * c, nrb=c, sra=1, srb=kk, nc=o, sc=c * kk), o, pl)
-            ops.gemm(M=mo, H=ho, W=wo, K=o, N=kk * c, a0=du, lda0=o, k0=o, wp=wct, out=dcd, ldo=kk * c)
-            _tap("rf.dcd", dcd)
-            # 4. ug
-            wg = gen_w.detach().float().reshape(c * kk, kk).contiguous()
-            ug = torch.empty((mo, kk * c), dtype=dt, device=dev)
-            es9 = xr.element_size() * mo * kk * c                 # bytes of one expanded tensor
-            with ops._Timed(f"ly_rf_generate_kernel<{ops._tname(xr)}, {k}>", 0.0, xr.element_size() * n * h * w * c + es9, valu_flops=2.0 * mo * kk * kk * c):
-                L.check(L.lib().ly_rf_generate(p(xr), ld, n, h, w, c, k, s, p(wg), p(ug), code, st), "ly_rf_generate")
-            # 5. cd, d_rfa, gmax, d_ca
-            cd = torch.empty((mo, kk * c), dtype=dt, device=dev)
-            zz = ops.zeros_f32(2 * rfa.numel() + ca.numel(), dev)
-            d_rfa, gmax, d_ca = zz[:rfa.numel()].view_as(rfa), zz[rfa.numel():2 * rfa.numel()].view_as(rfa), zz[2 * rfa.numel():].view_as(ca)
+            if ctx.rc is not None and dt == torch.bfloat16 and s == 2 and o in RC_BWD_WIDTHS:
+                return _rfcbam_backward_rc(ctx, sv, du, dgo, dbo)
             vw = ops.vw_of(xr)
-            rf3s = k == 3 and RF3S_BWD and c % vw == 0 and c // vw <= 64          # 16-bytes-per-lane passes (csrc/ly_rf1_bwd.hip: ly_rf3s_bwd)
-            if rf3s:
-                d_ca64 = ops.zeros_f64(ca.numel(), dev)                            # double accumulators: d_ca feeds dx through SE's backward
-                P3 = L.LyRf1BwdParams(n, ho * wo, c, p(ug), c, p(dcd), None, p(ag), p(bg), p(ca), p(rfa), p(cd), p(d_rfa), p(gmax), p(d_ca64),
-                                      p(gmax), None, None, None, None, None, None, 0.0, None, c, None, code)
-                with ops._Timed(f"ly_rf3s_bwd_kernel<{ops._tname(xr)}, 0>", 8.0 * mo * kk * c, 3.0 * es9):
-                    L.check(L.lib().ly_rf3s_bwd(ctypes.byref(P3), ho, wo, 0, st), "ly_rf3s_bwd 0")
-                d_ca = d_ca64                                            # read as doubles by ly_se_bwd
-            else:
-                with ops._Timed(f"ly_rf_bwd_attn_kernel<{ops._tname(xr)}, {k}>", 8.0 * mo * kk * c, 3.0 * es9):
-                    L.check(L.lib().ly_rf_bwd_attn(n, h, w, c, k, s, p(ug), p(dcd), p(ag), p(bg), p(ca), p(rfa), p(cd), p(d_rfa), p(gmax), p(d_ca), code, st),
-                            "ly_rf_bwd_attn")
-            _tap("rf.ug", ug); _tap("rf.cd", cd); _tap("rf.d_rfa", d_rfa); _tap("rf.gmax", gmax); _tap("rf.d_ca", d_ca)
-            _tap("rf.rfa", rfa); _tap("rf.ca", ca); _tap("rf.ag", ag); _tap("rf.bg", bg)
-            # 6. conv weight gradient
-            tgt = ops.grad_target(ctx.conv_w_param)            # k = 1: the weight's own layout is what ly_wgrad writes
-            if tgt is not None and kk == 1:
-                ops.wgrad(M=mo, H=ho, W=wo, N=o, du=du, lddu=o, x=cd, ldx=c, Hin=ho, Win=wo, Cin=c, dw=tgt, lddw=c)
-                ops.grad_done(ctx.conv_w_param)
-                dwc = None
-            elif _tap_major_rows(tgt) is not None:                  # k = 3 with a tap-major sink: [o][t][c] is the storage's own order
-                ops.wgrad(M=mo, H=ho, W=wo, N=o, du=du, lddu=o, x=cd, ldx=kk * c, Hin=ho, Win=wo, Cin=kk * c, dw=_tap_major_rows(tgt), lddw=kk * c)
-                ops.grad_done(ctx.conv_w_param)
-                dwc = None
-            else:
-                dwc = torch.zeros(o, kk * c, dtype=torch.float32, device=dev)      # handed to autograd (k = 1: as a view): not from the pool
-                ops.wgrad(M=mo, H=ho, W=wo, N=o, du=du, lddu=o, x=cd, ldx=kk * c, Hin=ho, Win=wo, Cin=kk * c, dw=dwc, lddw=kk * c)
-                dwc = dwc.view(o, kk, c).permute(0, 2, 1).reshape(conv_w.shape)
-            # 7. get_weight + sigmoid
-            w18 = getw.detach().float().reshape(18).contiguous()
-            d_mm = torch.empty_like(mm)
-            t18 = ops.grad_target(ctx.getw_param)
-            t18 = t18 if t18 is not None and t18.is_contiguous() else None
-            d18 = t18 is not None and ops.small_grads_ok()          # deferred: a float64 scratch, rounded into the sink when the backward pass ends
-            f18 = t18 is None and ops.DETERMINISTIC_SMALL_GRADS          # no sink: float64 scratch, rounded right away (returned to autograd)
-            dw18 = ops.small_grad_scratch(t18, ctx.getw_param) if d18 else t18.view(-1) if t18 is not None else \
-                ops.zeros_f64(18, dev) if f18 else torch.zeros(18, dtype=torch.float32, device=dev)
-            L.check(L.lib().ly_rfa_bwd(p(d_rfa), p(rfa), p(mm), p(w18), n, k * ho, k * wo, p(d_mm), p(dw18), int(d18 or f18), st), "ly_rfa_bwd")
-            if f18:
-                dw18 = ops.f64_round([dw18], [(18,)])[0]
-            if t18 is not None and not d18:
-                ops.grad_done(ctx.getw_param)
-            # 8. through max/mean, ca, rfa and ReLU; generate-BN sums
-            if rf3s:
-                sums = ops.new_stats(kk * c, dev)                                   # striped [STRIPES][2][9][c] doubles
-                P3.d_mm, P3.sums = p(d_mm), p(sums)
-                with ops._Timed(f"ly_rf3s_bwd_kernel<{ops._tname(xr)}, 1>", 8.0 * mo * kk * c, 3.0 * es9):
-                    L.check(L.lib().ly_rf3s_bwd(ctypes.byref(P3), ho, wo, 1, st), "ly_rf3s_bwd 1")
-            else:
-                sums = ops.zeros_f32(2 * kk * c, dev)
-                with ops._Timed(f"ly_rf_bwd_relu_kernel<{ops._tname(xr)}, {k}>", 8.0 * mo * kk * c, 3.0 * es9):
-                    L.check(L.lib().ly_rf_bwd_relu(n, h, w, c, k, s, p(ug), p(dcd), p(ag), p(bg), p(ca), p(rfa), p(gmax), p(d_mm), p(sums), code, st),
-                            "ly_rf_bwd_relu")
-            _tap("rf.d_mm", d_mm); _tap("rf.dv", dcd); _tap("rf.sums", sums)
-            # 9. generate BatchNorm coefficients ([t][c] order)
-            tgg, tgb = (ops.grad_target(q) for q in ctx.gen_bn_params)
-            bn_direct = all(q is not None and q.numel() == kk * c and q.is_contiguous() for q in (tgg, tgb))
-            dgg_tc, dbg_tc, alpha, kappa, lam = ops.bn_bwd_coeffs(sums, kk * c, mo, ag, gmean_tc, ginv_tc, True, dgamma=tgg if bn_direct else None,
-                                                                  dbeta=tgb if bn_direct else None, transpose=(kk, c))
-            if bn_direct:
-                ops.grad_done(ctx.gen_bn_params[0])
-                ops.grad_done(ctx.gen_bn_params[1])
-            ct = lambda v: None if v is None else v.view(kk, c).t().contiguous().view(-1)
-            # 10. dug, generate weight gradient
-            part_rows = 512
-            dwg = torch.zeros(part_rows, c * kk, kk, dtype=torch.float32, device=dev)         # per-block partial sums, summed below
-            with ops._Timed(f"ly_rf_bwd_gen_kernel<{ops._tname(xr)}, {k}>", 0.0, 3.0 * es9, valu_flops=2.0 * mo * kk * kk * c):
-                L.check(L.lib().ly_rf_bwd_gen(p(xr), ld, n, h, w, c, k, s, p(ug), p(dcd), p(alpha), p(kappa), p(lam), p(dwg), part_rows, code, st),
-                        "ly_rf_bwd_gen")
-            _tap("rf.coef", alpha); _tap("rf.dwg", dwg)
-            # 11. dx
-            # SE backward: parameter gradients, and d/d(mean x) which the dx kernel spreads over the pixels while it writes dx
-            se_wa, se_wb = ctx.se_params
-            ta, tb = ops.grad_target(se_wa), ops.grad_target(se_wb)
-            se_direct = ta is not None and tb is not None
-            dwa = ta if se_direct else torch.zeros(se_wa.shape, dtype=torch.float32, device=dev)
-            dwb = tb if se_direct else torch.zeros(se_wb.shape, dtype=torch.float32, device=dev)
-            dgap = ops.se_bwd(se_part, n, h * w, c, se_wa.detach(), se_wb.detach(), se_wa.shape[0], ca, d_ca, dwa, dwb)
-            if se_direct:
-                ops.grad_done(se_wa)
-                ops.grad_done(se_wb)
-            dx = None
-            if ctx.needs_input_grad[1]:
-                dx = ops.empty_nhwc(n, c, h, w, xr)
-                with ops._Timed(f"ly_rf_bwd_dx_kernel<{ops._tname(xr)}, {k}>", 0.0, es9 + xr.element_size() * n * h * w * c, valu_flops=2.0 * mo * kk * kk * c):
-                    L.check(L.lib().ly_rf_bwd_dx(n, h, w, c, k, s, p(dcd), p(wg), p(dx), c, p(dgap), 1.0 / (h * w), code, st), "ly_rf_bwd_dx")
-            dbias = None if ops.grad_target(ctx.conv_b_param) is not None else torch.zeros_like(bias)      # BN removes the batch mean: d/dbias = 0
-            tgw = ops.grad_target(ctx.gen_w_param)
-            if tgw is not None and tgw.is_contiguous() and tgw.numel() == dwg[0].numel():
-                ops.sum_rows(dwg, out=tgw.view(-1), accumulate=True)        # the partial rows of d(generate.0.weight) added straight into the sink
-                ops.grad_done(ctx.gen_w_param)
-                dgw = None
-            else:
-                dgw = ops.sum_rows(dwg).view(gen_w.shape)
-        return (None, dx, None if se_direct else dwa, None if se_direct else dwb, dgw, ct(dgg_tc), ct(dbg_tc),
-                (None if t18 is not None else dw18.view(getw.shape)), dwc, dbias, dgo, dbo)
+            if k == 1 and c % vw == 0 and c // vw <= 64 and ld % vw == 0:
+                return _rfcbam_backward_k1(ctx, sv, du, dgo, dbo)
+            return _rfcbam_backward_streamed(ctx, sv, du, dgo, dbo)
 
 
-def _rfcbam_backward_rc(ctx, du, dgo, dbo):
+# ---- the stages every backward route of RfcbamFn runs, in this order, between its own kernels.  sv: the saved tensors (_RfSaved) ----
+def _rf_getw_bwd(ctx, sv, d_rfa, hk, wk):
+    """get_weight conv + sigmoid backward over the [n, hk, wk] attention map -> d_mm (gradient of the max / mean maps), get_weight's return slot"""
+    L = _lib()
+    p = L.ptr
+    w18 = sv.getw.detach().float().reshape(18).contiguous()
+    d_mm = torch.empty_like(sv.mm)
+    g18 = ops.SmallGrad(ctx.getw_param, 18)
+    L.check(L.lib().ly_rfa_bwd(p(d_rfa), p(sv.rfa), p(sv.mm), p(w18), ctx.geom[0], hk, wk, p(d_mm), p(g18.buf), int(g18.f64), L.stream_ptr()), "ly_rfa_bwd")
+    return d_mm, g18.finish()
+
+
+def _rf_gen_bn_coeffs(ctx, sv, sums, ch, count, transpose):
+    """generate BatchNorm backward from the (striped) sums over its `ch` channels -> alpha, kappa, lambda of the passes that follow, and the
+    return slots of its weight and bias.  transpose = (t, c): the sums are in [t][c] order (k = 3), the parameters in [c][t]"""
+    tgg, tgb = (ops.grad_target(q) for q in ctx.gen_bn_params)
+    bn_direct = all(q is not None and q.numel() == ch and q.is_contiguous() for q in (tgg, tgb))
+    dgg, dbg, alpha, kappa, lam = ops.bn_bwd_coeffs(sums, ch, count, sv.ag, sv.gmean_tc, sv.ginv_tc, True, dgamma=tgg if bn_direct else None,
+                                                    dbeta=tgb if bn_direct else None, transpose=transpose)
+    if bn_direct:
+        ops.grad_done(ctx.gen_bn_params[0])
+        ops.grad_done(ctx.gen_bn_params[1])
+    elif transpose is not None:
+        dgg, dbg = dgg.view(transpose).t(), dbg.view(transpose).t()          # views: _rf_grads makes the copies, after the route's last kernel
+    return alpha, kappa, lam, dgg, dbg
+
+
+def _rf_se_bwd(ctx, sv, d_ca):
+    """SE backward: the parameter gradients -> d/d(mean x) [n, c], which the route's dx kernel spreads over the pixels while it writes dx, and the
+    return slots of the two linears.  d_ca: fp32 or float64 [n, c]"""
+    n, c, h, w = ctx.geom[:4]
+    se_wa, se_wb = ctx.se_params
+    ta, tb = ops.grad_target(se_wa), ops.grad_target(se_wb)
+    se_direct = ta is not None and tb is not None
+    dwa = ta if se_direct else torch.zeros(se_wa.shape, dtype=torch.float32, device=d_ca.device)
+    dwb = tb if se_direct else torch.zeros(se_wb.shape, dtype=torch.float32, device=d_ca.device)
+    dgap = ops.se_bwd(sv.se_part, n, h * w, c, se_wa.detach(), se_wb.detach(), se_wa.shape[0], sv.ca, d_ca, dwa, dwb)
+    if se_direct:
+        ops.grad_done(se_wa)
+        ops.grad_done(se_wb)
+        return dgap, None, None
+    return dgap, dwa, dwb
+
+
+def _rf_dbias(ctx, sv):
+    return None if ops.grad_target(ctx.conv_b_param) is not None else torch.zeros_like(sv.bias)      # BN removes the batch mean: d/dbias = 0
+
+
+def _rf_gen_w_fold(ctx, sv, dwg):
+    """rows of partial sums of d(generate.0.weight) -> its return slot (a contiguous sink takes the fold itself)"""
+    tgw = ops.grad_target(ctx.gen_w_param)
+    if tgw is not None and tgw.is_contiguous() and tgw.numel() == dwg[0].numel():
+        ops.sum_rows(dwg, out=tgw.view(-1), accumulate=True)
+        ops.grad_done(ctx.gen_w_param)
+        return None
+    return ops.sum_rows(dwg).view(sv.gen_w.shape)
+
+
+def _rf_grads(ctx, dx, dwa, dwb, dgw, dgg, dbg, dw18, dwc, dbias, dgo, dbo):
+    """the gradients in the order of RfcbamFn.forward's inputs.  dgg / dbg arrive in the parameters' [c][t] order, as flat vectors or as the
+    views _rf_gen_bn_coeffs makes: flattened HERE, so that the copies of a sink-less k = 3 pass launch behind the route's last kernel, as ever"""
+    flat = lambda v: None if v is None else v.reshape(-1)
+    return None, (dx if ctx.needs_input_grad[1] else None), dwa, dwb, dgw, flat(dgg), flat(dbg), dw18, dwc, dbias, dgo, dbo
+
+
+def _rfcbam_backward_streamed(ctx, sv, du, dgo, dbo):
+    """RFCBAMConv backward on 9x-sized tensors in HBM (csrc/ly_rfcbam_bwd.hip), every k and width: generate, attention, ReLU, generate weight
+    gradient and dx passes"""
+    xr, ca, gen_w, conv_w, ag, bg, rfa = sv.xr, sv.ca, sv.gen_w, sv.conv_w, sv.ag, sv.bg, sv.rfa
+    n, c, h, w, k, s, o, ho, wo, ld = ctx.geom
+    kk, mo = k * k, n * ho * wo
+    dev, dt = xr.device, xr.dtype
+    L = _lib()
+    st, p, code = L.stream_ptr(), L.ptr, L.dtype_code(xr)
+    # 3. dcd [mo][t][c]
+    # Wc^T with rows (t, c): conv.0.weight [o, c, kh, kw] read in place
+    dcd = torch.empty((mo, kk * c), dtype=dt, device=dev)
+    wct = pack.packed(pack.Src(ctx.conv_w_param, kk * c, nrb=c, sra=1, srb=kk, nc=o, sc=c * kk), o, ops.planes_of(xr))
+    ops.gemm(M=mo, H=ho, W=wo, K=o, N=kk * c, a0=du, lda0=o, k0=o, wp=wct, out=dcd, ldo=kk * c)
+    # 4. ug
+    wg = gen_w.detach().float().reshape(c * kk, kk).contiguous()
+    ug = torch.empty((mo, kk * c), dtype=dt, device=dev)
+    es9 = xr.element_size() * mo * kk * c                 # bytes of one expanded tensor
+    with ops._Timed(f"ly_rf_generate_kernel<{ops._tname(xr)}, {k}>", 0.0, xr.element_size() * n * h * w * c + es9, valu_flops=2.0 * mo * kk * kk * c):
+        L.check(L.lib().ly_rf_generate(p(xr), ld, n, h, w, c, k, s, p(wg), p(ug), code, st), "ly_rf_generate")
+    # 5. cd, d_rfa, gmax, d_ca
+    cd = torch.empty((mo, kk * c), dtype=dt, device=dev)
+    zz = ops.zeros_f32(2 * rfa.numel() + ca.numel(), dev)
+    d_rfa, gmax, d_ca = zz[:rfa.numel()].view_as(rfa), zz[rfa.numel():2 * rfa.numel()].view_as(rfa), zz[2 * rfa.numel():].view_as(ca)
+    vw = ops.vw_of(xr)
+    rf3s = k == 3 and c % vw == 0 and c // vw <= 64          # 16-bytes-per-lane passes (csrc/ly_rf1_bwd.hip: ly_rf3s_bwd)
+    if rf3s:
+        d_ca64 = ops.zeros_f64(ca.numel(), dev)                            # double accumulators: d_ca feeds dx through SE's backward
+        P3 = L.LyRf1BwdParams(n, ho * wo, c, p(ug), c, p(dcd), None, p(ag), p(bg), p(ca), p(rfa), p(cd), p(d_rfa), p(gmax), p(d_ca64),
+                              p(gmax), None, None, None, None, None, None, 0.0, None, c, None, code)
+        with ops._Timed(f"ly_rf3s_bwd_kernel<{ops._tname(xr)}, 0>", 8.0 * mo * kk * c, 3.0 * es9):
+            L.check(L.lib().ly_rf3s_bwd(ctypes.byref(P3), ho, wo, 0, st), "ly_rf3s_bwd 0")
+        d_ca = d_ca64                                            # read as doubles by ly_se_bwd
+    else:
+        with ops._Timed(f"ly_rf_bwd_attn_kernel<{ops._tname(xr)}, {k}>", 8.0 * mo * kk * c, 3.0 * es9):
+            L.check(L.lib().ly_rf_bwd_attn(n, h, w, c, k, s, p(ug), p(dcd), p(ag), p(bg), p(ca), p(rfa), p(cd), p(d_rfa), p(gmax), p(d_ca), code, st),
+                    "ly_rf_bwd_attn")
+    # 6. conv weight gradient
+    tgt = ops.grad_target(ctx.conv_w_param)            # k = 1: the weight's own layout is what ly_wgrad writes
+    if tgt is not None and kk == 1:
+        ops.wgrad(M=mo, H=ho, W=wo, N=o, du=du, lddu=o, x=cd, ldx=c, Hin=ho, Win=wo, Cin=c, dw=tgt, lddw=c)
+        ops.grad_done(ctx.conv_w_param)
+        dwc = None
+    elif _tap_major_rows(tgt) is not None:                  # k = 3 with a tap-major sink: [o][t][c] is the storage's own order
+        ops.wgrad(M=mo, H=ho, W=wo, N=o, du=du, lddu=o, x=cd, ldx=kk * c, Hin=ho, Win=wo, Cin=kk * c, dw=_tap_major_rows(tgt), lddw=kk * c)
+        ops.grad_done(ctx.conv_w_param)
+        dwc = None
+    else:
+        dwc = torch.zeros(o, kk * c, dtype=torch.float32, device=dev)      # handed to autograd (k = 1: as a view): not from the pool
+        ops.wgrad(M=mo, H=ho, W=wo, N=o, du=du, lddu=o, x=cd, ldx=kk * c, Hin=ho, Win=wo, Cin=kk * c, dw=dwc, lddw=kk * c)
+        dwc = dwc.view(o, kk, c).permute(0, 2, 1).reshape(conv_w.shape)
+    # 7. get_weight + sigmoid
+    d_mm, dw18 = _rf_getw_bwd(ctx, sv, d_rfa, k * ho, k * wo)
+    # 8. through max/mean, ca, rfa and ReLU; generate-BN sums
+    if rf3s:
+        sums = ops.new_stats(kk * c, dev)                                   # striped [STRIPES][2][9][c] doubles
+        P3.d_mm, P3.sums = p(d_mm), p(sums)
+        with ops._Timed(f"ly_rf3s_bwd_kernel<{ops._tname(xr)}, 1>", 8.0 * mo * kk * c, 3.0 * es9):
+            L.check(L.lib().ly_rf3s_bwd(ctypes.byref(P3), ho, wo, 1, st), "ly_rf3s_bwd 1")
+    else:
+        sums = ops.zeros_f32(2 * kk * c, dev)
+        with ops._Timed(f"ly_rf_bwd_relu_kernel<{ops._tname(xr)}, {k}>", 8.0 * mo * kk * c, 3.0 * es9):
+            L.check(L.lib().ly_rf_bwd_relu(n, h, w, c, k, s, p(ug), p(dcd), p(ag), p(bg), p(ca), p(rfa), p(gmax), p(d_mm), p(sums), code, st),
+                    "ly_rf_bwd_relu")
+    # 9. generate BatchNorm coefficients ([t][c] order)
+    alpha, kappa, lam, dgg, dbg = _rf_gen_bn_coeffs(ctx, sv, sums, kk * c, mo, (kk, c))
+    # 10. dug, generate weight gradient
+    part_rows = 512
+    dwg = torch.zeros(part_rows, c * kk, kk, dtype=torch.float32, device=dev)         # per-block partial sums, summed below
+    with ops._Timed(f"ly_rf_bwd_gen_kernel<{ops._tname(xr)}, {k}>", 0.0, 3.0 * es9, valu_flops=2.0 * mo * kk * kk * c):
+        L.check(L.lib().ly_rf_bwd_gen(p(xr), ld, n, h, w, c, k, s, p(ug), p(dcd), p(alpha), p(kappa), p(lam), p(dwg), part_rows, code, st),
+                "ly_rf_bwd_gen")
+    # 11. SE backward, dx
+    dgap, dwa, dwb = _rf_se_bwd(ctx, sv, d_ca)
+    dx = None
+    if ctx.needs_input_grad[1]:
+        dx = ops.empty_nhwc(n, c, h, w, xr)
+        with ops._Timed(f"ly_rf_bwd_dx_kernel<{ops._tname(xr)}, {k}>", 0.0, es9 + xr.element_size() * n * h * w * c, valu_flops=2.0 * mo * kk * kk * c):
+            L.check(L.lib().ly_rf_bwd_dx(n, h, w, c, k, s, p(dcd), p(wg), p(dx), c, p(dgap), 1.0 / (h * w), code, st), "ly_rf_bwd_dx")
+    dbias = _rf_dbias(ctx, sv)
+    return _rf_grads(ctx, dx, dwa, dwb, _rf_gen_w_fold(ctx, sv, dwg), dgg, dbg, dw18, dwc, dbias, dgo, dbo)
+
+
+def _rfcbam_backward_rc(ctx, sv, du, dgo, dbo):
     """RFCBAMConv k=3 backward on csrc/ly_rf3c_bwd.hip: no 9x-sized tensor in HBM — three recompute passes + the conv weight gradient"""
-    xr, ca, gen_w, getw, conv_w, bias, ag, bg, gmean_tc, ginv_tc, es, t, omean, oinv, mm, rfa, se_part, u = ctx.saved_tensors
+    xr, ca, conv_w, mm, rfa = sv.xr, sv.ca, sv.conv_w, sv.mm, sv.rfa
     n, c, h, w, k, s, o, ho, wo, ld = ctx.geom
     dev = xr.device
     L = _lib()
@@ -1222,13 +1216,10 @@ def _rfcbam_backward_rc(ctx, du, dgo, dbo):
     nog = -(-o // 128)
     ng = max(1, min(n, 256 // (nch * nog)))
     dwc_part = torch.empty((ng, o, 9, c), dtype=torch.float32, device=dev)
-    need_dx = ctx.needs_input_grad[1]
     dx = ops.empty_nhwc(n, c, h, w, xr)
     P = L.LyRf3cBwdParams(n, h, w, c, ho, wo, o, s, th, tw, p(xr), ld, p(du), o, p(wq), p(wct), p(ca), p(rfa), p(mm), None, None,
                           p(d_rfa_part), p(d_ca), p(sums), p(dwg), p(dx), c, None, 1.0 / (h * w), p(dwc_part), ng, L.dtype_code(xr))
-    es9 = 2.0 * mo * 9 * c
     xb = xr.element_size() * (n * h * w * c + mo * o)
-    tn = ops._tname(xr)
     # A: d_rfa (one slab per channel chunk), d_ca
     with ops._Timed(f"ly_rf3c_bwd_kernel<0, {o // 32}>", 2.0 * mo * 9 * c * o, xb, valu_flops=2.0 * mo * c * 81):
         L.check(L.lib().ly_rf3c_bwd(ctypes.byref(P), 0, st), "ly_rf3c_bwd A")
@@ -1245,69 +1236,31 @@ def _rfcbam_backward_rc(ctx, du, dgo, dbo):
         dwc = dwc.permute(0, 2, 1).reshape(conv_w.shape)
     # get_weight + sigmoid
     d_rfa = ops.sum_rows(d_rfa_part).view_as(rfa) if nch > 1 else d_rfa_part[0].view_as(rfa)
-    w18 = getw.detach().float().reshape(18).contiguous()
-    d_mm = torch.empty_like(mm)
-    t18 = ops.grad_target(ctx.getw_param)
-    t18 = t18 if t18 is not None and t18.is_contiguous() else None
-    d18 = t18 is not None and ops.small_grads_ok()          # deferred: a float64 scratch, rounded into the sink when the backward pass ends
-    f18 = t18 is None and ops.DETERMINISTIC_SMALL_GRADS          # no sink: float64 scratch, rounded right away (returned to autograd)
-    dw18 = ops.small_grad_scratch(t18, ctx.getw_param) if d18 else t18.view(-1) if t18 is not None else \
-        ops.zeros_f64(18, dev) if f18 else torch.zeros(18, dtype=torch.float32, device=dev)
-    L.check(L.lib().ly_rfa_bwd(p(d_rfa), p(rfa), p(mm), p(w18), n, 3 * ho, 3 * wo, p(d_mm), p(dw18), int(d18 or f18), st), "ly_rfa_bwd")
-    if f18:
-        dw18 = ops.f64_round([dw18], [(18,)])[0]
-    if t18 is not None and not d18:
-        ops.grad_done(ctx.getw_param)
+    d_mm, dw18 = _rf_getw_bwd(ctx, sv, d_rfa, 3 * ho, 3 * wo)
     P.d_mm = p(d_mm)
     # B: BatchNorm sums, one stripe per image
     with ops._Timed(f"ly_rf3c_bwd_kernel<1, {o // 32}>", 2.0 * mo * 9 * c * o, xb, valu_flops=2.0 * mo * c * 81):
         L.check(L.lib().ly_rf3c_bwd(ctypes.byref(P), 1, st), "ly_rf3c_bwd B")
-    tgg, tgb = (ops.grad_target(q) for q in ctx.gen_bn_params)
-    bn_direct = all(q is not None and q.numel() == 9 * c and q.is_contiguous() for q in (tgg, tgb))
-    dgg_tc, dbg_tc, alpha, kappa, lam = ops.bn_bwd_coeffs(sums, 9 * c, mo, ag, gmean_tc, ginv_tc, True, dgamma=tgg if bn_direct else None,
-                                                          dbeta=tgb if bn_direct else None, transpose=(9, c))
-    if bn_direct:
-        ops.grad_done(ctx.gen_bn_params[0])
-        ops.grad_done(ctx.gen_bn_params[1])
+    alpha, kappa, lam, dgg, dbg = _rf_gen_bn_coeffs(ctx, sv, sums, 9 * c, mo, (9, c))
     P.coef = p(alpha)                          # alpha, kappa, lambda are rows 2..4 of one [5, 9c] tensor
     assert kappa.data_ptr() == alpha.data_ptr() + 4 * 9 * c and lam.data_ptr() == alpha.data_ptr() + 8 * 9 * c
-    ct = lambda v: None if v is None else v.view(9, c).t().contiguous().view(-1)
-    # SE backward: parameter gradients, and d/d(mean x) which pass C adds while it writes dx
-    se_wa, se_wb = ctx.se_params
-    ta, tb = ops.grad_target(se_wa), ops.grad_target(se_wb)
-    se_direct = ta is not None and tb is not None
-    dwa = ta if se_direct else torch.zeros(se_wa.shape, dtype=torch.float32, device=dev)
-    dwb = tb if se_direct else torch.zeros(se_wb.shape, dtype=torch.float32, device=dev)
-    dgap = ops.se_bwd(se_part, n, h * w, c, se_wa.detach(), se_wb.detach(), se_wa.shape[0], ca, d_ca, dwa, dwb)
-    if se_direct:
-        ops.grad_done(se_wa)
-        ops.grad_done(se_wb)
+    # SE backward; d/d(mean x) is added by pass C while it writes dx
+    dgap, dwa, dwb = _rf_se_bwd(ctx, sv, d_ca)
     P.dgap = p(dgap)
     P.TH, P.TW = ops.pick_tile_bwd_dx(ho, wo, o)          # pass C walks its pixel pairs in four colours: its own tile choice
     # C: generate weight gradient rows + dx
     # pass C: regenerate (81 MAC) + generate weight gradient (81) + dx (81) per (output pixel, channel) on the VALU; dG = W^T du on the MFMAs
     with ops._Timed(f"ly_rf3c_bwd_kernel<2, {o // 32}>", 2.0 * mo * 9 * c * o, xb + xr.element_size() * n * h * w * c, valu_flops=2.0 * mo * c * 243):
         L.check(L.lib().ly_rf3c_bwd(ctypes.byref(P), 2, st), "ly_rf3c_bwd C")
-    dbias = None if ops.grad_target(ctx.conv_b_param) is not None else torch.zeros_like(bias)      # BN removes the batch mean: d/dbias = 0
-    tgw = ops.grad_target(ctx.gen_w_param)
-    if tgw is not None and tgw.is_contiguous() and tgw.numel() == dwg.shape[1]:
-        ops.sum_rows(dwg, out=tgw.view(-1), accumulate=True)            # the image rows of d(generate.0.weight) added straight into the sink
-        ops.grad_done(ctx.gen_w_param)
-        dgw = None
-    else:
-        dgw = ops.sum_rows(dwg).view(gen_w.shape)
-    return (None, dx if need_dx else None, None if se_direct else dwa, None if se_direct else dwb, dgw, ct(dgg_tc), ct(dbg_tc),
-            (None if t18 is not None else dw18.view(getw.shape)), dwc, dbias, dgo, dbo)
+    dbias = _rf_dbias(ctx, sv)
+    return _rf_grads(ctx, dx, dwa, dwb, _rf_gen_w_fold(ctx, sv, dwg), dgg, dbg, dw18, dwc, dbias, dgo, dbo)      # (dwg: one row per image)
 
 
-RfcbamFn._backward_rc = staticmethod(_rfcbam_backward_rc)
-
-
-def _rfcbam_backward_k1(ctx, du, dgo, dbo):
+def _rfcbam_backward_k1(ctx, sv, du, dgo, dbo):
     """RFCBAMConv kernel_size 1 backward on the fused recompute passes (csrc/ly_rf1_bwd.hip): G = relu(bn(gw*x)) is recomputed from x in
     every pass, nothing the size of the input is stored except cd (the conv weight gradient's operand) and dx.  du: gradient of the conv
     output (after the output BatchNorm / ReLU backward)."""
-    xr, ca, gen_w, getw, conv_w, bias, ag, bg, gmean_tc, ginv_tc, es, t, omean, oinv, mm, rfa, se_part, u = ctx.saved_tensors
+    xr, ca, gen_w, conv_w, ag, bg, rfa = sv.xr, sv.ca, sv.gen_w, sv.conv_w, sv.ag, sv.bg, sv.rfa
     n, c, h, w, k, s, o, ho, wo, ld = ctx.geom
     dev, dt = xr.device, xr.dtype
     L = _lib()
@@ -1320,23 +1273,17 @@ def _rfcbam_backward_k1(ctx, du, dgo, dbo):
     ops.gemm(M=mo, H=h, W=w, K=o, N=c, a0=du, lda0=o, k0=o, wp=wct, out=dcd, ldo=c)
     gw = gen_w.detach().float().reshape(c).contiguous()
     cd = torch.empty((mo, c), dtype=dt, device=dev)
-    d_ca64 = ops.zeros_f64(ca.numel(), dev)                 # double accumulators: d_ca feeds dx through SE's backward
+    d_ca = ops.zeros_f64(ca.numel(), dev)                 # double accumulators (read as doubles by ly_se_bwd): d_ca feeds dx through SE's backward
     d_rfa = torch.empty(rfa.numel(), dtype=torch.float32, device=dev)
     gmax = torch.empty(rfa.numel(), dtype=torch.float32, device=dev)
-    dx = ops.empty_nhwc(n, c, h, w, xr) if ctx.needs_input_grad[1] else ops.empty_nhwc(n, c, h, w, xr)
-    tgw = ops.grad_target(ctx.gen_w_param) if getattr(ctx, "gen_w_param", None) is not None else None
-    tgw = tgw if tgw is not None and tgw.is_contiguous() else None
-    dgw_defer = tgw is not None and ops.small_grads_ok()
-    dgw_fresh64 = tgw is None and ops.DETERMINISTIC_SMALL_GRADS         # no sink: float64 scratch, rounded after pass C (returned to autograd)
-    dgw = ops.small_grad_scratch(tgw, ctx.gen_w_param) if dgw_defer else tgw.view(-1) if tgw is not None else \
-        ops.zeros_f64(c, dev) if dgw_fresh64 else torch.zeros(c, dtype=torch.float32, device=dev)
-    P = L.LyRf1BwdParams(n, h * w, c, p(xr), ld, p(dcd), p(gw), p(ag), p(bg), p(ca), p(rfa), p(cd), p(d_rfa), p(gmax), p(d_ca64),
-                         p(gmax), None, None, None, None, None, None, 1.0 / (h * w), p(dx), c, p(dgw), L.dtype_code(xr), int(dgw_defer or dgw_fresh64))
+    dx = ops.empty_nhwc(n, c, h, w, xr)                   # (pass C writes it whether or not it is asked for)
+    ggw = ops.SmallGrad(ctx.gen_w_param, c)               # pass C adds the generate weight gradient; finished after it
+    P = L.LyRf1BwdParams(n, h * w, c, p(xr), ld, p(dcd), p(gw), p(ag), p(bg), p(ca), p(rfa), p(cd), p(d_rfa), p(gmax), p(d_ca),
+                         p(gmax), None, None, None, None, None, None, 1.0 / (h * w), p(dx), c, p(ggw.buf), L.dtype_code(xr), int(ggw.f64))
     es1 = xr.element_size() * mo * c
     tn = ops._tname(xr)
     with ops._Timed(f"ly_rf1_bwd_kernel<{tn}, 0>", 6.0 * mo * c, 3.0 * es1):
         L.check(L.lib().ly_rf1_bwd(ctypes.byref(P), 0, st), "ly_rf1_bwd A")
-    d_ca = d_ca64                                            # read as doubles by ly_se_bwd
     # conv weight gradient from cd
     tgt = ops.grad_target(ctx.conv_w_param)
     if tgt is not None:
@@ -1348,58 +1295,25 @@ def _rfcbam_backward_k1(ctx, du, dgo, dbo):
         ops.wgrad(M=mo, H=h, W=w, N=o, du=du, lddu=o, x=cd, ldx=c, Hin=h, Win=w, Cin=c, dw=dwc, lddw=c)
         dwc = dwc.view(conv_w.shape)
     # get_weight + sigmoid
-    w18 = getw.detach().float().reshape(18).contiguous()
-    d_mm = torch.empty_like(mm)
-    t18 = ops.grad_target(ctx.getw_param)
-    t18 = t18 if t18 is not None and t18.is_contiguous() else None
-    d18 = t18 is not None and ops.small_grads_ok()          # deferred: a float64 scratch, rounded into the sink when the backward pass ends
-    f18 = t18 is None and ops.DETERMINISTIC_SMALL_GRADS          # no sink: float64 scratch, rounded right away (returned to autograd)
-    dw18 = ops.small_grad_scratch(t18, ctx.getw_param) if d18 else t18.view(-1) if t18 is not None else \
-        ops.zeros_f64(18, dev) if f18 else torch.zeros(18, dtype=torch.float32, device=dev)
-    L.check(L.lib().ly_rfa_bwd(p(d_rfa), p(rfa), p(mm), p(w18), n, h, w, p(d_mm), p(dw18), int(d18 or f18), st), "ly_rfa_bwd")
-    if f18:
-        dw18 = ops.f64_round([dw18], [(18,)])[0]
-    if t18 is not None and not d18:
-        ops.grad_done(ctx.getw_param)
+    d_mm, dw18 = _rf_getw_bwd(ctx, sv, d_rfa, h, w)
     # BatchNorm sums of the generate BatchNorm (double accumulators)
     sums = ops.new_stats(c, dev)
     P.d_mm, P.sums = p(d_mm), p(sums)
     with ops._Timed(f"ly_rf1_bwd_kernel<{tn}, 1>", 8.0 * mo * c, 2.0 * es1):
         L.check(L.lib().ly_rf1_bwd(ctypes.byref(P), 1, st), "ly_rf1_bwd B")
-    tgg, tgb = (ops.grad_target(q) for q in ctx.gen_bn_params)
-    bn_direct = tgg is not None and tgb is not None and tgg.numel() == c and tgb.numel() == c and tgg.is_contiguous() and tgb.is_contiguous()
-    dgg, dbg, alpha, kappa, lam = ops.bn_bwd_coeffs(sums, c, mo, ag, gmean_tc, ginv_tc, True, dgamma=tgg if bn_direct else None,
-                                                    dbeta=tgb if bn_direct else None)
-    if bn_direct:
-        ops.grad_done(ctx.gen_bn_params[0])
-        ops.grad_done(ctx.gen_bn_params[1])
-    # SE backward: parameter gradients, and d/d(mean x), which pass C adds while it writes dx
-    se_wa, se_wb = ctx.se_params
-    ta, tb = ops.grad_target(se_wa), ops.grad_target(se_wb)
-    se_direct = ta is not None and tb is not None
-    dwa = ta if se_direct else torch.zeros(se_wa.shape, dtype=torch.float32, device=dev)
-    dwb = tb if se_direct else torch.zeros(se_wb.shape, dtype=torch.float32, device=dev)
-    dgap = ops.se_bwd(se_part, n, h * w, c, se_wa.detach(), se_wb.detach(), se_wa.shape[0], ca, d_ca, dwa, dwb)
-    if se_direct:
-        ops.grad_done(se_wa)
-        ops.grad_done(se_wb)
+    alpha, kappa, lam, dgg, dbg = _rf_gen_bn_coeffs(ctx, sv, sums, c, mo, None)
+    # SE backward; d/d(mean x) is added by pass C while it writes dx
+    dgap, dwa, dwb = _rf_se_bwd(ctx, sv, d_ca)
     P.alpha, P.kappa, P.lambda_, P.dgap = p(alpha), p(kappa), p(lam), p(dgap)
     with ops._Timed(f"ly_rf1_bwd_kernel<{tn}, 2>", 10.0 * mo * c, 3.0 * es1):
         L.check(L.lib().ly_rf1_bwd(ctypes.byref(P), 2, st), "ly_rf1_bwd C")
-    if dgw_fresh64:
-        dgw = ops.f64_round([dgw], [(c,)])[0]
-    if tgw is not None and not dgw_defer:
-        ops.grad_done(ctx.gen_w_param)
-    dbias = None if ops.grad_target(ctx.conv_b_param) is not None else torch.zeros_like(bias)      # BN removes the batch mean: d/dbias = 0
-    return (None, dx if ctx.needs_input_grad[1] else None, None if se_direct else dwa, None if se_direct else dwb,
-            None if tgw is not None else dgw.view(gen_w.shape), dgg, dbg, (None if t18 is not None else dw18.view(getw.shape)), dwc, dbias, dgo, dbo)
+    dgw = ggw.finish()
+    return _rf_grads(ctx, dx, dwa, dwb, dgw, dgg, dbg, dw18, dwc, _rf_dbias(ctx, sv), dgo, dbo)
 
 
-RfcbamFn._backward_k1 = staticmethod(_rfcbam_backward_k1)
-RF1_BWD = True         # tools: False keeps the first-generation k = 1 backward
-RF3S_BWD = True        # tools: False keeps the thread = channel attention / ReLU passes of the streamed k = 3 backward
-RC_BWD = True          # tools: False keeps the first-generation backward behind the lane = channel forward
 RC_BWD_WIDTHS = (64, 128)           # output widths on the recompute passes (see RfcbamFn.backward); a module constant: tools / tests monkeypatch it
+
+
 def rfcbam_train(mod, x):
     """RFCBAMConv.forward in training: one autograd node (SE, generate BatchNorm, attention maps, contraction)."""
     g, cv = mod.generate, mod.conv

@@ -704,6 +704,33 @@ def _flush_small_items(items):
             grad_done(prm)
 
 
+class SmallGrad:
+    """Where ONE parameter's small gradient of `numel` values goes.  `buf` is what the kernel ADDS into, `f64` says whether it holds doubles;
+    `finish()` is called once the kernel that fills it is in the stream.  The sink's storage is taken when it is contiguous and holds `numel`
+    values: as a deferred float64 scratch inside a backward pass, directly outside the engine.  Without it the values go back to autograd,
+    through a fresh float64 buffer (DETERMINISTIC_SMALL_GRADS) or a plain fp32 one.
+    `numel` is the parameter's own element count at every site (Detect's bias: na * no, get_weight: 18, the k = 1 generate weight: c), and a
+    sink target has its parameter's shape: the size test only ever refused a Detect bias of another length, and still does; the value handed
+    to autograd has the parameter's shape, as autograd demands."""
+
+    def __init__(self, param, numel):
+        t = grad_target(param)
+        self.param = param
+        self.target = t = t if t is not None and t.is_contiguous() and t.numel() == numel else None
+        self.deferred = t is not None and small_grads_ok()        # rounded into the sink when the backward pass ends
+        self.f64 = self.deferred or (t is None and DETERMINISTIC_SMALL_GRADS)
+        self.buf = small_grad_scratch(t, param) if self.deferred else t.view(-1) if t is not None else \
+            zeros_f64(numel, param.device) if self.f64 else torch.zeros(numel, dtype=torch.float32, device=param.device)      # (handed to autograd: not from the pool)
+
+    def finish(self):
+        """-> what the autograd function returns for the parameter (None: the gradient went to the sink)"""
+        if self.target is None:
+            return f64_round([self.buf], [self.param.shape])[0] if self.f64 else self.buf.view(self.param.shape)
+        if not self.deferred:
+            grad_done(self.param)               # (a deferred gradient is announced by flush_small_grads)
+        return None
+
+
 def mlpblock(x, y, n, h, w, c, wp, w1, w2, sc, sh, stats=None):
     m = n * h * w
     cc, nt, ht, t2d = mlp_config(c, m, w, x.dtype == torch.bfloat16)
@@ -816,20 +843,6 @@ def stats_pool_end():
     p = _POOL
     p.active = False
     p.need = max(p.need, p.used)
-
-
-def new_sums(nch, device):
-    """zeroed striped FLOAT accumulator [STRIPES][2*nch] of a backward reduction (ly_bnact_bwd_reduce, ly_rf*_bwd -> ly_bn_bwd_coeffs)"""
-    p = _POOL
-    n = STRIPES * 2 * nch
-    if p.active:
-        span = (n + 63) // 64 * 64                  # 256-byte aligned slices
-        p.used += span
-        if p.buf is not None and p.buf.device == device and p.off + span <= p.buf.numel():
-            v = p.buf[p.off:p.off + n].view(STRIPES, 2 * nch)
-            p.off += span
-            return v
-    return torch.zeros(STRIPES, 2 * nch, dtype=torch.float32, device=device)
 
 
 _ONES = {}

@@ -118,9 +118,31 @@ BWD_CASES = [
 ]
 
 
-@pytest.mark.parametrize("kind,ctor,shape", BWD_CASES)
-def test_module_backward_shapes_vs_oracle(kind, ctor, shape):
-    """real layer shapes and ragged sizes: every gradient elementwise against autograd through the oracle"""
+def _sink_on(m, monkeypatch):
+    """an optim.FusedSGD over m's parameters, as train.py builds it.  Its first step() creates the persistent gradient storage and installs
+    ops.SINK (put back when the test ends); the gradients are zero there, so the weights stay as they are.  From then on the backward kernels
+    add straight into `p.grad`."""
+    from lead_yolo_amd import ops, optim
+    monkeypatch.setattr(ops, "SINK", ops.SINK)
+    opt = optim.FusedSGD(m.parameters())
+    opt.step()
+    assert all(ops.grad_target(p) is p.grad for p in m.parameters())
+    opt.zero_grad()
+
+
+def _with_sink_cases(cases, pick):
+    """every case without the gradient sink under the id it always had, and the cases `pick` selects once more with it"""
+    ids = ["-".join(v if isinstance(v, str) else f"{name}{i}" for name, v in zip(("kind", "ctor", "shape")[-len(case):], case))
+           for i, case in enumerate(cases)]
+    return [pytest.param(*case, False, id=i) for case, i in zip(cases, ids)] + \
+        [pytest.param(*case, True, id=i + "-sink") for case, i in zip(cases, ids) if pick(case)]
+
+
+@pytest.mark.parametrize("kind,ctor,shape,sink", _with_sink_cases(BWD_CASES, lambda case: case[0] == "RFCBAMConv"))
+def test_module_backward_shapes_vs_oracle(kind, ctor, shape, sink, monkeypatch):
+    """real layer shapes and ragged sizes: every gradient elementwise against autograd through the oracle.  sink: the RFCBAMConv routes
+    (k = 1 recompute, streamed with ly_rf3s_bwd, ragged, streamed thread = channel passes, generic k = 1) once more with the parameter
+    gradients written straight into an optimiser's storage"""
     torch.manual_seed(0)
     m = _ctor(kind)(*ctor)
     st = synth.synth_state(synth.shapes_of(m.state_dict()), 9100 + sum(shape) + len(kind))
@@ -133,7 +155,10 @@ def test_module_backward_shapes_vs_oracle(kind, ctor, shape):
     # (5e-6 forward differences), and one flipped element changes every gradient by O(1) * r there
     r = r * (y0.abs() > 1e-4)
     yo, dxo, gpo = _oracle_grads(kind, ctor, st, x, r)
-    y, dx, gp = _hip_grads(m.to(_dev()).train(), x, r)
+    m = m.to(_dev()).train()
+    if sink:
+        _sink_on(m, monkeypatch)
+    y, dx, gp = _hip_grads(m, x, r)
     _close(y, yo, f"{kind}{ctor} y")
     _close(dx, dxo, f"{kind}{ctor} dx")
     for k, want in gpo.items():

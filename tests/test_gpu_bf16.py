@@ -21,6 +21,7 @@ import torch
 from oracle import functional as OF
 from oracle import synth
 from tests import golden_util as G
+from tests.test_gpu_backward import _sink_on, _with_sink_cases
 from tests.test_gpu_modules import CASES, GOLDEN_MODULES, _bn_eps, _cfg, _ctor, _dev, _load, _oracle
 
 pytestmark = pytest.mark.gpu
@@ -106,14 +107,16 @@ def test_module_train_forward_and_backward_bf16(name):
     _close(got, want, name + " dx", rel=0.15 if routing else 2 * REL_L2, mx=2.0 if routing else 4 * MAX_REL)     # routing: single entries may move by their whole value
 
 
-@pytest.mark.parametrize("ctor,shape", [((64, 64, 3, 2), (2, 64, 24, 24)), ((128, 128, 3, 2), (2, 128, 16, 16)), ((256, 256, 3, 2), (1, 256, 16, 16)),
-                                        ((32, 48, 3, 1), (2, 32, 9, 14)), ((64, 128, 1, 1), (2, 64, 12, 12))])
-def test_rfcbam_backward_bf16_smooth_case(ctor, shape):
+@pytest.mark.parametrize("ctor,shape,sink", _with_sink_cases(
+    [((64, 64, 3, 2), (2, 64, 24, 24)), ((128, 128, 3, 2), (2, 128, 16, 16)), ((256, 256, 3, 2), (1, 256, 16, 16)),
+     ((32, 48, 3, 1), (2, 32, 9, 14)), ((64, 128, 1, 1), (2, 64, 12, 12))], lambda case: True))
+def test_rfcbam_backward_bf16_smooth_case(ctor, shape, sink, monkeypatch):
     """RFCBAMConv backward in bf16 WITHOUT routing decisions, at the smooth-module bound (the 15 % band of the routing modules
     must not be the only check of ly_rf*_bwd / ly_rf3c_bwd / ly_rf1_bwd).  Both BatchNorms get gamma = 0.1, beta = 1: every pre-ReLU value
     is 1 + 0.1 * xhat > 0 (no kinks), channel 0's generate-BatchNorm gets beta = 2: the channel maximum is channel 0 everywhere, by a
     margin no bf16 rounding closes (no flipped arg-max), and SE's hidden ReLU sees positive weights on a positive pooled input.  What is left is smooth, so the input gradient and the weight gradients must meet
-    2 * 8 * 2^-8 relative L2 and cosine >= 0.995 against the fp32 oracle — a wrong-by-10 % tap weight in any backward kernel fails this."""
+    2 * 8 * 2^-8 relative L2 and cosine >= 0.995 against the fp32 oracle — a wrong-by-10 % tap weight in any backward kernel fails this.  sink: the same, with the parameter gradients written
+    straight into an optimiser's storage (rows 0-1: recompute route, row 2: streamed with ly_rf3s_bwd, row 3: stride 1, row 4: k = 1)."""
     from tests.test_gpu_backward import _oracle_grads
     c, o, k, s = ctor
     torch.manual_seed(0)
@@ -133,6 +136,8 @@ def test_rfcbam_backward_bf16_smooth_case(ctor, shape):
     r = synth.synth_input((shape[0], o, ho, wo), 43 + o)
     y0, dx0, g0 = _oracle_grads("RFCBAMConv", list(ctor), st, x, r)
     m = m.to(_dev()).train()
+    if sink:                                                     # the parameter gradients go straight into an optimiser's storage
+        _sink_on(m, monkeypatch)
     xt = x.to(_dev()).to(BF).requires_grad_(True)
     with torch.autocast("cuda", dtype=BF):
         y = m(xt)

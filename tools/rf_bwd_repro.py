@@ -1,5 +1,5 @@
 """Run-to-run stability of the RFCBAMConv k=3 backward (bf16): the same module step N times from one state, per-tensor differences between
-runs, for the recompute backward (csrc/ly_rf3c_bwd.hip, grad.RC_BWD = True) and the streamed one.   python tools/rf_bwd_repro.py"""
+runs, for the recompute backward (csrc/ly_rf3c_bwd.hip) and the streamed one (grad.RC_BWD_WIDTHS = ()).   python tools/rf_bwd_repro.py"""
 import os
 import sys
 
@@ -14,6 +14,7 @@ dev = torch.device("cuda:0")
 BF = torch.bfloat16
 names = ("conv.0.weight", "generate.0.weight", "generate.1.weight", "generate.1.bias", "conv.1.weight", "conv.1.bias", "se.fc.0.weight", "se.fc.2.weight",
          "get_weight.0.weight")
+widths = grad.RC_BWD_WIDTHS
 for ctor, shape in (((64, 64, 3, 2), (4, 64, 48, 48)), ((128, 128, 3, 2), (4, 128, 40, 40))):
     c, o, k, s = ctor
     torch.manual_seed(0)
@@ -27,7 +28,7 @@ for ctor, shape in (((64, 64, 3, 2), (4, 64, 48, 48)), ((128, 128, 3, 2), (4, 12
     x = synth.synth_input(shape, 77).to(dev).to(BF)
     r = synth.synth_input((shape[0], o, shape[2] // s, shape[3] // s), 78).to(dev).to(BF)
     for rc in (True, False):
-        grad.RC_BWD = rc
+        grad.RC_BWD_WIDTHS = widths if rc else ()
         outs = []
         for _ in range(6):
             for p in m.parameters():
@@ -45,4 +46,4 @@ for ctor, shape in (((64, 64, 3, 2), (4, 64, 48, 48)), ((128, 128, 3, 2), (4, 12
             d = max(float((o_[i] - base).abs().max()) for o_ in outs[1:])
             rep.append(f"{nm} {d / (float(base.abs().max()) + 1e-30):.1e}")
         print(" | ".join(rep), flush=True)
-grad.RC_BWD = True
+grad.RC_BWD_WIDTHS = widths
