@@ -24,14 +24,7 @@ from . import ops, pack
 from .ops import ACT_NONE, ACT_RELU, ACT_SILU  # noqa: F401
 
 
-def _rows_dense(t):
-    """NHWC-dense view of a logical [n, c, h, w] tensor (copy only if needed)."""
-    t = ops.nhwc(t)
-    if t.stride(1) != 1:
-        t = t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    return t
-
-
+_rows_dense = ops.rows_dense
 
 
 # ---- tensors with two consumers: the sum of the two gradients as a store ----------------------------------------------------------------
@@ -110,49 +103,18 @@ class ConvSpec:
 
 
 
-def _conv_forward(spec, x0, x1, wp, e_scale, e_shift, act, stats=None, out=None, store=False):
+def _source(spec, x0, x1):
+    """what ops.conv_unit reads for `spec`: the Lazy over the one or two row sources of a 1x1 unit, else the tensor"""
+    return ops.Lazy.of(x0, x1, spec.up) if spec.kind == "pw" else x0
+
+
+def _conv_forward(spec, x0, x1, wp, e_scale, e_shift, act, stats=None, store=False):
     """Runs the forward contraction of `spec`; returns the output tensor (None for a pure statistics pass; with store=True a
     statistics pass also stores its pre-BN value, in the same launch)."""
-    co = spec.cout
-    if spec.kind == "pw":
-        t0, ld0 = ops.rows(x0)
-        n, c0, h, w = t0.shape
-        if spec.up:
-            h, w = 2 * h, 2 * w
-        kw = dict(a0=t0, lda0=ld0, k0=c0, gather=ops.GATHER_UP2 if spec.up else ops.GATHER_ROWS)
-        k = c0
-        if x1 is not None:
-            t1, ld1 = ops.rows(x1)
-            kw.update(a1=t1, lda1=ld1)
-            k += t1.shape[1]
-        if (stats is None or store) and out is None:
-            out = ops.empty_nhwc(n, co, h, w, t0)
-        ops.gemm(M=n * h * w, H=h, W=w, K=k, N=co, wp=wp, out=out, ldo=co, e_scale=e_scale, e_shift=e_shift, act=act, stats=stats, **kw)
-        return out
-    if spec.kind == "c3":
-        t0, ld0 = ops.rows(x0)
-        n, c, h, w = t0.shape
-        if (stats is None or store) and out is None:
-            out = ops.empty_nhwc(n, co, h, w, t0)
-        ops.conv3x3(M=n * h * w, H=h, W=w, Cin=c, N=co, x=t0, ldx=ld0, wp=wp, out=out, ldo=co, e_scale=e_scale, e_shift=e_shift, act=act,
-                    stats=stats)
-        return out
-    n, c, h, w = x0.shape
-    k = spec.k
-    ho, wo = h // k, w // k
-    if spec.nchw:
-        xr = x0.contiguous()
-        kw = dict(K=16 * c, a0=xr, lda0=0, k0=16 * c, gather=ops.GATHER_PATCH_NCHW, Hin=h, Win=w, Cin=c, ks=4, pk=0)
-    else:
-        xr = _rows_dense(x0)
-        kw = dict(K=k * k * c, a0=xr, lda0=c, k0=k * k * c, gather=ops.GATHER_PATCH, Hin=h, Win=w, Cin=c, ks=k, pk=k * c)
-    odt = spec.out_dtype or xr.dtype
-    if (stats is None or store) and out is None:
-        out = ops.empty_nhwc(n, co, ho, wo, xr, dtype=odt)
-    ops.gemm(M=n * ho * wo, H=ho, W=wo, N=co, wp=wp, out=out, ldo=co, e_scale=e_scale, e_shift=e_shift, act=act, stats=stats, dtype=odt, **kw)
+    src = _source(spec, x0, x1)
+    out = ops.unit_out(spec.kind, src, spec.cout, spec.k, spec.out_dtype) if (stats is None or store) else None
+    ops.conv_unit(spec.kind, src, wp, spec.cout, e_scale, e_shift, act, stats=stats, out=out, k=spec.k, nchw=spec.nchw, dtype=spec.out_dtype)
     return out
-
-
 
 
 def affine_backward(dy, u, a, b, act, mean, invstd, train, inplace=True, gamma=None, beta=None, lddy=None, out=None):
@@ -186,16 +148,8 @@ def conv_wgrad(spec, du, x0, x1, weight):
     tgt = ops.grad_target(weight)
     dw = tgt if tgt is not None else torch.zeros(weight.shape, dtype=torch.float32, device=du.device)
     if spec.kind == "pw":
-        t0, ld0 = ops.rows(x0)
-        c0 = t0.shape[1]
-        k = c0 + (x1.shape[1] if x1 is not None else 0)
-        probs = [dict(M=m, H=ho, W=wo, N=co, du=du, lddu=co, x=t0, ldx=ld0, Hin=t0.shape[2], Win=t0.shape[3], Cin=c0, dw=dw, lddw=k,
-                      up2=spec.up, n_valid=nv)]
-        if x1 is not None:
-            t1, ld1 = ops.rows(x1)
-            probs.append(dict(M=m, H=ho, W=wo, N=co, du=du, lddu=co, x=t1, ldx=ld1, Hin=ho, Win=wo, Cin=t1.shape[1], dw=dw, lddw=k, dw_off=c0,
-                              n_valid=nv))
-        ops.wgrad_group(probs)               # two row sources (a concat read in place): one launch when both are plain rows
+        # two row sources (a concat read in place): one launch when both are plain rows
+        ops.wgrad_group(_pw_wgrad_problems(du, co, 0, co, _source(spec, x0, x1), dw, n_valid=nv))
     elif spec.kind == "c3":
         t0, ld0 = ops.rows(x0)
         c = t0.shape[1]
@@ -245,6 +199,35 @@ def conv_wgrad(spec, du, x0, x1, weight):
     return dw
 
 
+def _pw_wgrad_problems(du, lddu, du_off, N, src, dw, n_valid=None, dup=None):
+    """The ops.wgrad problems of a 1x1 unit, one per row source of `src` (a Lazy without gate): dw [N, kin] (row stride kin = all input
+    channels; the second source's columns start at c0) += columns du_off.. of du [n, ., ho, wo]^T . source.  A lazily upsampled first source
+    is gathered by the kernel (up2) — or, given dup = du with the upsample's adjoint already applied (ops.up2_bwd), contracted as plain
+    rows at a quarter of the pixels."""
+    n, kin, ho, wo = src.shape
+    m, c0 = n * ho * wo, src.k0
+    to = dict(N=N, lddu=lddu, du_off=du_off, dw=dw, lddw=kin, n_valid=n_valid)
+    if dup is not None:
+        probs = [dict(M=m // 4, H=ho // 2, W=wo // 2, du=dup, x=src.a0, ldx=src.lda0, Hin=ho // 2, Win=wo // 2, Cin=c0, **to)]
+    else:
+        probs = [dict(M=m, H=ho, W=wo, du=du, x=src.a0, ldx=src.lda0, Hin=src.a0.shape[2], Win=src.a0.shape[3], Cin=c0, up2=src.up, **to)]
+    if src.a1 is not None:
+        probs.append(dict(M=m, H=ho, W=wo, du=du, x=src.a1, ldx=src.lda1, Hin=ho, Win=wo, Cin=kin - c0, dw_off=c0, **to))
+    return probs
+
+
+def _pw_dgrad(du, wt, kin, c0, up, need0, need1):
+    """(dx0, dx1) of a 1x1 unit: ONE contraction of du [n, co, ho, wo] with the transposed weight image wt over all kin input channels,
+    split at c0 between the two sources (c0 == kin: one source); a lazily upsampled first source takes the sum over each 2x2 block"""
+    n, co, ho, wo = du.shape
+    d = ops.empty_nhwc(n, kin, ho, wo, du)
+    ops.gemm(M=n * ho * wo, H=ho, W=wo, K=co, N=kin, a0=du, lda0=co, k0=co, wp=wt, out=d, ldo=kin)
+    d0 = None
+    if need0:
+        d0 = ops.up2_bwd(d, kin, n, ho // 2, wo // 2, c0) if up else d if c0 == kin else d[:, :c0]
+    return d0, (d[:, c0:] if need1 and c0 < kin else None)
+
+
 def _tap_major_rows(g):
     """[co, kh*kw*ci] row view of the [co][kh][kw][ci] storage behind a tap-major gradient target (see _tap_major), else None"""
     if g is None or not _tap_major(g):
@@ -273,15 +256,7 @@ def conv_dgrad(spec, du, weight, x0, x1, need0, need1, slots=(None, None)):
             wt = pack.packed(pack.src_matrix(weight, kin, nw, sr=1, sk=kin, k_pad=co), co, ops.planes_of(du))
             if x1 is None and not spec.up and slots[0] is not None and kin % 4 == 0:
                 return _gemm_dx(slots[0], n, kin, ho, wo, du, M=m, H=ho, W=wo, K=co, N=kin, a0=du, lda0=co, k0=co, wp=wt, ldo=kin), None
-            d = ops.empty_nhwc(n, kin, ho, wo, du)
-            ops.gemm(M=m, H=ho, W=wo, K=co, N=kin, a0=du, lda0=co, k0=co, wp=wt, out=d, ldo=kin)
-            if x1 is None:
-                return (ops.up2_bwd(d, kin, n, ho // 2, wo // 2, kin) if spec.up else d), None
-            c0 = x0.shape[1]
-            d0 = d[:, :c0]
-            if spec.up and need0:
-                d0 = ops.up2_bwd(d, kin, n, ho // 2, wo // 2, c0)
-            return (d0 if need0 else None), (d[:, c0:] if need1 else None)
+            return _pw_dgrad(du, wt, kin, x0.shape[1] if x1 is not None else kin, spec.up, need0 or x1 is None, need1)
         if spec.kind == "c3":
             cop = (weight.shape[0] + 31) // 32 * 32
             wt = pack.packed(pack.src_taps(weight, cop, transposed_flipped=True), 9 * cop, ops.planes_of(du))
@@ -313,7 +288,7 @@ class ConvBnAct(torch.autograd.Function):
         dev = x0.device
         ctx.slots = (_slot_of(x0), _slot_of(x1))
         bias_f = bias.detach().float().contiguous() if bias is not None else None
-        mean = invstd = None
+        mean = invstd = u = None
         if spec.bn is not None:
             if spec.bn_train and co % 4 == 0:
                 # ONE contraction: statistics and the pre-BN value u in the same launch; y = act(a*u + b) is an elementwise
@@ -324,31 +299,27 @@ class ConvBnAct(torch.autograd.Function):
                 a, b, mean, invstd = ops.bn_finalize(spec.bn, stats, co, rows, want_stats=True)
                 y = torch.empty_like(u)
                 ops.bnact_fwd(u, co, rows, co, a, b, spec.act, y, co)
-                ctx.spec, ctx.wp = spec, wp
-                ctx.has = (x1 is not None, bias is not None)
-                ctx.params = (weight, gamma, beta)
-                ctx.save_for_backward(x0, x1, weight, bias_f, a, b, mean, invstd, u)
-                return y
-            elif spec.bn_train:
-                stats = ops.new_stats(co, dev)
-                _conv_forward(spec, x0, x1, wp, None, bias_f, ACT_NONE, stats=stats)
-                y0 = _out_shape(spec, x0)
-                a, b, mean, invstd = ops.bn_finalize(spec.bn, stats, co, y0[0] * y0[2] * y0[3], want_stats=True)
             else:
-                bn = spec.bn
-                invstd = torch.rsqrt(bn.running_var.detach().float() + bn.eps)
-                mean = bn.running_mean.detach().float()
-                a = (gamma.detach().float() * invstd).contiguous()
-                b = (beta.detach().float() - mean * a).contiguous()
-            sh = b if bias_f is None else (b + bias_f * a).contiguous()
-            y = _conv_forward(spec, x0, x1, wp, a, sh, spec.act)
+                if spec.bn_train:
+                    stats = ops.new_stats(co, dev)
+                    _conv_forward(spec, x0, x1, wp, None, bias_f, ACT_NONE, stats=stats)
+                    y0 = _out_shape(spec, x0)
+                    a, b, mean, invstd = ops.bn_finalize(spec.bn, stats, co, y0[0] * y0[2] * y0[3], want_stats=True)
+                else:
+                    bn = spec.bn
+                    invstd = torch.rsqrt(bn.running_var.detach().float() + bn.eps)
+                    mean = bn.running_mean.detach().float()
+                    a = (gamma.detach().float() * invstd).contiguous()
+                    b = (beta.detach().float() - mean * a).contiguous()
+                sh = b if bias_f is None else (b + bias_f * a).contiguous()
+                y = _conv_forward(spec, x0, x1, wp, a, sh, spec.act)
         else:
             a = b = None
             y = _conv_forward(spec, x0, x1, wp, None, bias_f, spec.act)
         ctx.spec, ctx.wp = spec, wp
         ctx.has = (x1 is not None, bias is not None)
         ctx.params = (weight, gamma, beta)
-        ctx.save_for_backward(x0, x1, weight, bias_f, a, b, mean, invstd, None)
+        ctx.save_for_backward(x0, x1, weight, bias_f, a, b, mean, invstd, u)         # u: kept for the backward, or None (recomputed there)
         return y
 
     @staticmethod
@@ -477,10 +448,8 @@ class ConvBnActPair(torch.autograd.Function):
         out = [None] * 12
         with torch.no_grad():
             du = torch.empty_like(u)
-            t0, ld0 = ops.rows(x0)
-            c0 = t0.shape[1]
-            t1, ld1 = ops.rows(x1) if x1 is not None else (None, 0)
-            kin = c0 + (t1.shape[1] if t1 is not None else 0)
+            src = _source(spec, x0, x1)
+            c0, kin = src.k0, src.shape[1]
             # the two weight gradients as ONE stacked [2c_, kin] matrix when the sink keeps them adjacent (optim.FusedSGD does)
             tw = [ops.grad_target(ctx.params[i][0]) for i in range(2)]
             stacked = (need[6] and need[7] and tw[0] is not None and tw[1] is not None and tw[0].is_contiguous() and tw[1].is_contiguous()
@@ -518,28 +487,20 @@ class ConvBnActPair(torch.autograd.Function):
             # not an upsample-gathering weight gradient at full resolution plus a full-resolution data gradient folded afterwards.
             hq, wq, rq = ho // 2, wo // 2, rows // 4
             dup = ops.up2_bwd(du, co, n, hq, wq, co) if spec.up else None
-            p0 = (dict(M=rq, H=hq, W=wq, du=dup, lddu=co, x=t0, ldx=ld0, Hin=hq, Win=wq, Cin=c0, lddw=kin) if spec.up else
-                  dict(M=rows, H=ho, W=wo, du=du, lddu=co, x=t0, ldx=ld0, Hin=t0.shape[2], Win=t0.shape[3], Cin=c0, lddw=kin))
             for i in range(2):
                 off = i * c_
                 w_p = ctx.params[i][0]
                 if need[6 + i] and not stacked:
                     tgt = tw[i]
                     dw = tgt if tgt is not None else torch.zeros(w_p.shape, dtype=torch.float32, device=u.device)
-                    ops.wgrad(N=c_, du_off=off, dw=dw, **p0)
-                    if t1 is not None:
-                        ops.wgrad(M=rows, H=ho, W=wo, N=c_, du=du, lddu=co, du_off=off, x=t1, ldx=ld1, Hin=ho, Win=wo, Cin=t1.shape[1], dw=dw,
-                                  lddw=kin, dw_off=c0)
+                    for q in _pw_wgrad_problems(du, co, off, c_, src, dw, dup=dup):
+                        ops.wgrad(**q)
                     if tgt is not None:
                         ops.grad_done(w_p)
                     else:
                         out[6 + i] = dw
             if stacked:
-                probs = [dict(N=co, dw=tw[0], **p0)]
-                if t1 is not None:
-                    probs.append(dict(M=rows, H=ho, W=wo, N=co, du=du, lddu=co, x=t1, ldx=ld1, Hin=ho, Win=wo, Cin=t1.shape[1], dw=tw[0], lddw=kin,
-                                      dw_off=c0))
-                ops.wgrad_group(probs)
+                ops.wgrad_group(_pw_wgrad_problems(du, co, 0, co, src, tw[0], dup=dup))
                 ops.grad_done(ctx.params[0][0])
                 ops.grad_done(ctx.params[1][0])
             s0, s1 = ctx.slots
@@ -557,18 +518,8 @@ class ConvBnActPair(torch.autograd.Function):
                 out[4] = _gemm_dx(s0, n, kin, ho, wo, du, M=rows, H=ho, W=wo, K=co, N=kin, a0=du, lda0=co, k0=co,
                                   wp=pack.packed(ctx.wt_src, co, ops.planes_of(du)), ldo=kin)
             elif need[4] or need[5]:
-                pl = ops.planes_of(du)
-                d = ops.empty_nhwc(n, kin, ho, wo, du)
                 # [W1^T | W2^T] ([kin, 2c_]) read in place from the two parameters: ONE contraction over both halves of du
-                wt = pack.packed(ctx.wt_src, co, pl)
-                ops.gemm(M=rows, H=ho, W=wo, K=co, N=kin, a0=du, lda0=co, k0=co, wp=wt, out=d, ldo=kin)
-                if x1 is None:
-                    out[4] = d
-                else:
-                    if need[4]:
-                        out[4] = d[:, :c0]
-                    if need[5]:
-                        out[5] = d[:, c0:]
+                out[4], out[5] = _pw_dgrad(du, pack.packed(ctx.wt_src, co, ops.planes_of(du)), kin, c0, False, need[4] or x1 is None, need[5])
         return tuple(out)
 
 
@@ -576,9 +527,6 @@ def conv_bn_act_pair(act, up, wp, x0, x1, conv1, bn1, conv2, bn2):
     """cv1(x), cv2(x) of two Conv modules sharing their input, as one node (see ConvBnActPair)"""
     spec = ConvSpec("pw", conv1.weight.shape[0] + conv2.weight.shape[0], act, bn1, True, up=up)
     return ConvBnActPair.apply(spec, wp, bn1, bn2, x0, x1, conv1.weight, conv2.weight, bn1.weight, bn1.bias, bn2.weight, bn2.bias)
-
-
-FUSED_DETECT_LEVEL = True      # development switch: False = head GEMM + ly_detect_tail in the training forward (measured 25-50 us per step slower)
 
 
 class DetectHeadFn(torch.autograd.Function):
@@ -596,10 +544,10 @@ class DetectHeadFn(torch.autograd.Function):
         bias_f = bias.detach().float().contiguous()
         bs, cin, ny, nx = x.shape
         p = torch.empty((bs, det.na, ny, nx, det.no), dtype=torch.float32, device=x.device)
-        t0, ld = ops.rows(x)
-        if FUSED_DETECT_LEVEL and ops.detect_level_ok(cin, det.na, det.no, t0.dtype) and ld % ops.vw_of(t0) == 0 and t0.data_ptr() % 16 == 0:
+        fused = ops.detect_level_rows(x, cin, det.na, det.no)
+        if fused is not None:
             # head contraction + permute in one launch (csrc/ly_detect.hip), on the step's packed weights as they are
-            ops.detect_level(t0, ld, bs, ny, nx, cin, wp, bias_f, det.na, det.no, det.anchors[i], 1.0, p, None, 0, 0, nat=False)
+            ops.detect_level(fused[0], fused[1], bs, ny, nx, cin, wp, bias_f, det.na, det.no, det.anchors[i], 1.0, p, None, 0, 0, nat=False)
         else:
             y = _conv_forward(spec, x, None, wp, None, bias_f, ACT_NONE)
             ops.detect_tail(y, co, bs, ny, nx, det.na, det.no, det.anchors[i], 1.0, p, None, 0, 0)
@@ -635,17 +583,15 @@ class DetectHeadFn(torch.autograd.Function):
 
 def detect_head(det, i, wp, x, weight, bias):
     """Detect level i in training -> fp32 raw map [bs, na, ny, nx, no]; the fused node when the map fits its kernel, else the generic
-    conv node + autograd's permute."""
+    conv node + autograd's permute.  wp: the packed weight the fused node contracts with; the generic branch takes its operands from
+    Detect._head_operands (the same image, or the 2-plane one beside a widened bf16 map)."""
     co = weight.shape[0]
     n, _, h, w = x.shape
     if w <= DetectHeadFn.MAXW and (co + 7) // 8 * 8 <= DetectHeadFn.MAXLD and bias is not None:
         return DetectHeadFn.apply(det, i, wp, x, weight, bias)
-    if x.dtype == torch.bfloat16:
-        # the generic conv node stores its output in the storage type: a bf16 head output would round the raw map (up to 2^-8 of the value)
-        # on its way to the loss and sum the bias gradient from a bf16 du.  The map is widened (exact; autograd rounds dx back to bf16) and
-        # the head runs in fp32 storage, like Detect._head in eval.  Cost not measured: the copy and an fp32 contraction per level.
-        x = x.float()
-        wp, _ = det._packed(i, 2)
+    # the generic conv node stores its output in the storage type: a bf16 map is widened first (Detect._head_operands), or a bf16 head output
+    # would round the raw map on its way to the loss and the bias gradient would be summed from a bf16 du
+    x, wp, _ = det._head_operands(i, x)
     y = conv_bn_act(ConvSpec("pw", co), wp, x, None, weight, bias, None)
     p = torch.empty((n, det.na, h, w, det.no), dtype=torch.float32, device=y.device)
     p.copy_(y.view(n, det.na, det.no, h, w).permute(0, 1, 3, 4, 2))

@@ -20,10 +20,9 @@ the eval path.
 """
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import ops, pack
-from .ops import ACT_NONE, ACT_RELU, ACT_SILU
+from .ops import ACT_NONE, ACT_RELU, ACT_SILU, Lazy
 
 BN_EPS = 1e-3
 BN_MOMENTUM = 0.03
@@ -122,56 +121,16 @@ def _act_code(act):
     raise NotImplementedError(f"activation {type(act).__name__} is not built into the HIP epilogues (SiLU / ReLU / identity)")
 
 
-class Lazy:
-    """A not-yet-materialised activation a consumer GEMM can absorb: channel concat of up to two row
-    sources, the first optionally at half resolution (nearest 2x upsample) or gated by CoordAtt."""
+def _affine_eval(prep, conv, bn):
+    """(scale, shift) of the eval epilogue of conv(+bias) -> [bn]: the BatchNorm's running statistics folded with the bias, cached in
+    `prep` until one of the tensors changes"""
+    key = pack.versions(conv.bias, *(_bn_tensors(bn) if bn is not None else ())) + (bn.eps if bn is not None else 0,)
 
-    def __init__(self, shape, a0, lda0, k0, a1=None, lda1=0, up=False, gate=None, keep=()):
-        self.shape = shape          # logical (n, c, h, w)
-        self.a0, self.lda0, self.k0 = a0, lda0, k0
-        self.a1, self.lda1 = a1, lda1
-        self.up = up
-        self.gate = gate            # (a_h, a_w) or None
-        self.keep = keep            # tensors kept alive
-
-    @staticmethod
-    def of(x):
-        if isinstance(x, Lazy):
-            return x
-        t, ld = ops.rows(x)
-        n, c, h, w = t.shape
-        return Lazy((n, c, h, w), t, ld, c, keep=(t,))
-
-    def materialize(self):
-        n, c, h, w = self.shape
-        if self.gate is not None:
-            assert self.a1 is None and not self.up
-            return ops.coordatt_gate(self.a0, self.lda0, n, h, w, c, self.gate[0], self.gate[1])
-        parts = []
-        a0 = self.keep[0]
-        if self.up:
-            a0 = F.interpolate(a0, scale_factor=2, mode="nearest")
-        parts.append(a0)
-        if self.a1 is not None:
-            parts.append(self.keep[1])
-        return parts[0] if len(parts) == 1 else torch.cat(parts, 1)
-
-
-def _run_pointwise(src, wp, n_out, e_scale, e_shift, act, out=None, ldo=None):
-    """GEMM over a Lazy / tensor source -> NHWC tensor [n, n_out, h, w] (or into `out` rows)."""
-    L = Lazy.of(src)
-    n, c, h, w = L.shape
-    if out is None:
-        res = ops.empty_nhwc(n, n_out, h, w, L.a0)
-        out_t, ldo = res, n_out
-    else:
-        res, out_t = None, out
-    kw = dict(M=n * h * w, H=h, W=w, K=c, N=n_out, a0=L.a0, lda0=L.lda0, k0=L.k0, a1=L.a1, lda1=L.lda1, wp=wp, out=out_t,
-              ldo=ldo, e_scale=e_scale, e_shift=e_shift, act=act, gather=ops.GATHER_UP2 if L.up else ops.GATHER_ROWS)
-    if L.gate is not None:
-        kw.update(pro=ops.PRO_GATE, g_h=L.gate[0], g_w=L.gate[1])
-    ops.gemm(**kw)
-    return res
+    def build():
+        if bn is not None:
+            return pack.bn_scale_shift(bn, conv.bias)
+        return None, (conv.bias.detach().float().contiguous() if conv.bias is not None else None)
+    return prep.get(key, build)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -318,18 +277,6 @@ class _PatchConv(nn.Module):
             return pack.packed(pack.src_taps(w, ci), kh * kw * ci, planes)      # columns (ky, kx, c): the NHWC patch gather's order
         return self._prep.get(key, build, planes)
 
-    def _affine_eval(self):
-        conv = getattr(self, self._conv_name)
-        bn = getattr(self, "norm", None)
-        has_bn = isinstance(bn, nn.BatchNorm2d)
-        key = pack.versions(conv.bias, *(_bn_tensors(bn) if has_bn else ())) + (bn.eps if has_bn else 0,)
-
-        def build():
-            if has_bn:
-                return pack.bn_scale_shift(bn, conv.bias)
-            return None, (conv.bias.detach().float().contiguous() if conv.bias is not None else None)
-        return self._prep_bn.get(key, build)
-
     def forward(self, x):
         pr = _probe(x, (x.shape[0], self.cout, x.shape[2] // self.k, x.shape[3] // self.k))
         if pr is not None:
@@ -361,34 +308,20 @@ class _PatchConv(nn.Module):
             return ops.edge_out(self._fwd(x, nchw, odt), back)
 
     def _fwd(self, x, nchw, odt):
-        n, c, h, w = x.shape
-        k = self.k
-        ho, wo = h // k, w // k
+        c, k = x.shape[1], self.k
         planes = 2 if nchw else ops.planes_of(odt)       # the image gather contracts in bf16x3 (fp32 source) whatever the output dtype
         if not nchw and c % ops.vw_of(odt) != 0:
             raise NotImplementedError(f"{type(self).__name__}: {odt} patch gathers need channels % {ops.vw_of(odt)} == 0 (got {c})")
-        if self.training and isinstance(getattr(self, "norm", None), nn.BatchNorm2d):
+        conv, bn = getattr(self, self._conv_name), getattr(self, "norm", None)
+        bn = bn if isinstance(bn, nn.BatchNorm2d) else None
+        wp = self._weights(nchw, planes)
+        if self.training and bn is not None:
             from . import grad
-            if nchw and (k != 4 or w % 4 != 0):
-                raise NotImplementedError("HIP patch embedding of an NCHW image needs patch_size 4 and W % 4 == 0")
-            conv = getattr(self, self._conv_name)
-            spec = grad.ConvSpec("patch", self.cout, ACT_NONE, self.norm, True, k=k, nchw=nchw, out_dtype=odt)
-            return grad.conv_bn_act(spec, self._weights(nchw, planes), x, None, conv.weight, conv.bias, self.norm)
-        if c % 4 == 0:
-            xr, ld = ops.rows(x)
-            if ld != c:
-                xr, ld = ops.nhwc(x.contiguous()), c
-            kw = dict(M=n * ho * wo, H=ho, W=wo, K=k * k * c, N=self.cout, a0=xr, lda0=c, k0=k * k * c, wp=self._weights(False, planes),
-                      ldo=self.cout, gather=ops.GATHER_PATCH, Hin=h, Win=w, Cin=c, ks=k, pk=k * c, dtype=odt)
-        else:
-            if k != 4 or w % 4 != 0:
-                raise NotImplementedError("HIP patch embedding of an NCHW image needs patch_size 4 and W % 4 == 0")
-            xr = x.contiguous()                     # NCHW image
-            kw = dict(M=n * ho * wo, H=ho, W=wo, K=16 * c, N=self.cout, a0=xr, lda0=0, k0=16 * c, wp=self._weights(True, planes),
-                      ldo=self.cout, gather=ops.GATHER_PATCH_NCHW, Hin=h, Win=w, Cin=c, ks=4, pk=0, dtype=odt)
-        sc, sh = self._affine_eval()
-        out = ops.empty_nhwc(n, self.cout, ho, wo, x, dtype=odt)
-        ops.gemm(out=out, e_scale=sc, e_shift=sh, **kw)
+            spec = grad.ConvSpec("patch", self.cout, ACT_NONE, bn, True, k=k, nchw=nchw, out_dtype=odt)
+            return grad.conv_bn_act(spec, wp, x, None, conv.weight, conv.bias, bn)
+        sc, sh = _affine_eval(self._prep_bn, conv, bn)
+        out = ops.unit_out("patch", x, self.cout, k, odt)
+        ops.conv_unit("patch", x, wp, self.cout, sc, sh, ACT_NONE, out=out, k=k, nchw=nchw, dtype=odt)
         return out
 
     def fuseforward(self, x):
@@ -453,24 +386,11 @@ class Conv(nn.Module):
             return pack.packed(pack.src_taps(w, cip), 9 * cip, planes)
         return self._prep.get(key, build, planes)
 
-    def affine_eval(self):
-        conv, bn = self.conv, getattr(self, "bn", None)
-        key = pack.versions(conv.bias, *(_bn_tensors(bn) if bn is not None else ())) + (bn.eps if bn is not None else 0,)
-
-        def build():
-            if bn is not None:
-                return pack.bn_scale_shift(bn, conv.bias)
-            return None, (conv.bias.detach().float().contiguous() if conv.bias is not None else None)
-        return self._prep_bn.get(key, build)
-
     def _run(self, x, sc, sh, act):
         wp = self.weights(ops.planes_of(x.a0 if isinstance(x, Lazy) else x))
-        if self.k == 1:
-            return _run_pointwise(x, wp, self.c2, sc, sh, act)
-        xr, ld = ops.rows(x)
-        n, c, h, w = xr.shape
-        out = ops.empty_nhwc(n, self.c2, h, w, xr)
-        ops.conv3x3(M=n * h * w, H=h, W=w, Cin=c, N=self.c2, x=xr, ldx=ld, wp=wp, out=out, ldo=self.c2, e_scale=sc, e_shift=sh, act=act)
+        kind, src = ("pw", Lazy.of(x)) if self.k == 1 else ("c3", x)
+        out = ops.unit_out(kind, src, self.c2)
+        ops.conv_unit(kind, src, wp, self.c2, sc, sh, act, out=out)
         return out
 
     @_edge
@@ -489,19 +409,14 @@ class Conv(nn.Module):
             # is kept.  Inference only: train-mode batch statistics would have to be taken over the kept pixels.
             if self.training:
                 raise NotImplementedError("HIP Conv with stride 2 is built for inference (eval mode) only")
-            sc, sh = self.affine_eval()
+            sc, sh = _affine_eval(self._prep_bn, self.conv, bn)
             return self._run(x, sc, sh, act)[:, :, ::2, ::2].contiguous(memory_format=torch.channels_last)
         if self.training and bn is not None:
             from . import grad
-            x0, x1, up = x, None, False
-            if isinstance(x, Lazy):
-                if x.gate is not None:
-                    x0 = x.materialize()
-                else:
-                    x0, x1, up = x.keep[0], (x.keep[1] if x.a1 is not None else None), x.up
+            x0, x1, up = ops.sources(x)
             spec = grad.ConvSpec("pw" if self.k == 1 else "c3", self.c2, act, bn, True, up=up)
             return grad.conv_bn_act(spec, self.weights(ops.planes_of(x0)), x0, x1, self.conv.weight, self.conv.bias, bn)
-        sc, sh = self.affine_eval()
+        sc, sh = _affine_eval(self._prep_bn, self.conv, bn)
         return self._run(x, sc, sh, act)
 
     def forward_fuse(self, x):
@@ -828,9 +743,7 @@ class C3_CA(nn.Module):
         from . import grad
         if pack.src_matrix_kcat_t(p1.conv.weight, p2.conv.weight) is None:
             return self.cv1(x), self.cv2(x)
-        x0, x1, up = x, None, False
-        if isinstance(x, Lazy):
-            x0, x1, up = x.keep[0], (x.keep[1] if x.a1 is not None else None), x.up
+        x0, x1, up = ops.sources(x)
         return grad.conv_bn_act_pair(_act_code(p1.act), up, self._weights12(ops.planes_of(x0)), x0, x1, p1.conv, b1, p2.conv, b2)
 
     def _affine12_eval(self):
@@ -840,13 +753,9 @@ class C3_CA(nn.Module):
                             *(_bn_tensors(b2) if b2 is not None else ()))
 
         def build():
-            parts = []
-            for p, b in ((p1, b1), (p2, b2)):
-                if b is not None:
-                    parts.append(pack.bn_scale_shift(b, p.conv.bias))
-                else:
-                    parts.append((torch.ones(self.c_, device=p.conv.weight.device), p.conv.bias.detach().float()))
-            return torch.cat((parts[0][0], parts[1][0])).contiguous(), torch.cat((parts[0][1], parts[1][1])).contiguous()
+            (s1, t1), (s2, t2) = _affine_eval(p1._prep_bn, p1.conv, b1), _affine_eval(p2._prep_bn, p2.conv, b2)
+            s1, s2 = (torch.ones_like(t) if s is None else s for s, t in ((s1, t1), (s2, t2)))      # (a unit without BatchNorm)
+            return torch.cat((s1, s2)).contiguous(), torch.cat((t1, t2)).contiguous()
         return self._prep_bn.get(key, build)
 
     @_edge
@@ -870,7 +779,7 @@ class C3_CA(nn.Module):
         wp = self._weights12(ops.planes_of(src.a0))
         sc, sh = self._affine12_eval()
         ycat = ops.empty_nhwc(n, 2 * c_, h, w, src.a0)
-        _run_pointwise(src, wp, 2 * c_, sc, sh, _act_code(self.cv1.act), out=ycat, ldo=2 * c_)
+        ops.conv_unit("pw", src, wp, 2 * c_, sc, sh, _act_code(self.cv1.act), out=ycat)
         cur = Lazy((n, c_, h, w), ycat, 2 * c_, c_, keep=(ycat,))
         for blk in self.m:
             cur = Lazy.of(blk.forward_lazy(cur))
@@ -949,9 +858,6 @@ class Concat(nn.Module):
         return torch.cat(x, self.d)
 
 
-FUSED_DETECT_LEVEL = True      # development switch: False sends Detect levels through the GEMM + ly_detect_tail pair
-
-
 class Detect(nn.Module):
     stride = None
     dynamic = False
@@ -983,32 +889,43 @@ class Detect(nn.Module):
         return self._prep[i].get(key, lambda: (pack.frag_pack_nat(conv.weight.detach().float().view(conv.out_channels, conv.in_channels), planes),
                                                conv.bias.detach().float().contiguous()), ("nat", planes))
 
-    def _fused_level_input(self, i, xi):
-        """the feature map as dense rows when the one-launch level kernel takes it (plain tensor, shape built), else None"""
-        if isinstance(xi, Lazy) or not isinstance(xi, torch.Tensor) or xi.dim() != 4 or not FUSED_DETECT_LEVEL:
-            return None
-        conv = self.m[i]
-        if conv.bias is None or not ops.detect_level_ok(conv.in_channels, self.na, self.no, xi.dtype):
-            return None
-        rows, ld = ops.rows(xi)
-        return (rows, ld) if ld % ops.vw_of(xi.dtype) == 0 and rows.data_ptr() % 16 == 0 else None
+    def _head_operands(self, i, x):
+        """(x, packed weight, fp32 bias) of level i's head GEMM, on every route that misses the one-launch kernels (eval: na*no > 32, Lazy
+        inputs, misaligned rows, augmented passes; training: grad.detect_head's generic node).  The GEMM stores in its own element type: a
+        bf16 buffer would round the raw map (up to 2^-8 of the value) before the tail / the loss reads it, while ly_detect_level hands its
+        fp32 accumulators on.  Raw maps leave Detect as fp32 on every route: a bf16 feature map is widened (exact; in training autograd
+        rounds dx back to bf16) and the head contracts in fp32 storage with the 2-plane weight image.  The cost — a full fp32 copy of the
+        map and a bf16x3 contraction per level — has not been measured (the benchmark runs nc = 1); a GEMM with a bf16 source and an fp32
+        destination would avoid the copy."""
+        if (x.a0 if isinstance(x, Lazy) else x).dtype == torch.bfloat16:
+            x = (x.materialize() if isinstance(x, Lazy) else x).float()
+        return (x,) + self._packed(i, ops.planes_of(x.a0 if isinstance(x, Lazy) else x))
 
     def _head(self, i, x):
         conv = self.m[i]
+        x, wp, b = self._head_operands(i, x)
         L = Lazy.of(x)
-        if L.a0.dtype == torch.bfloat16:
-            # the GEMM stores in its own element type: a bf16 buffer would round the raw map (up to 2^-8 of the value) before the tail reads
-            # it, while ly_detect_level hands its fp32 accumulators on.  Raw maps leave Detect as fp32 on every route: the feature map is
-            # widened (exact) and the head contracts in fp32 storage.  The cost — a full fp32 copy of the map and a bf16x3 contraction for
-            # every level that misses the one-launch kernel (na*no > 32, Lazy inputs, misaligned rows; eval and augmented passes) — has not
-            # been measured (the benchmark runs nc = 1); a GEMM with a bf16 source and an fp32 destination would avoid the copy
-            L = Lazy.of((x.materialize() if isinstance(x, Lazy) else x).float())
-        wp, b = self._packed(i, ops.planes_of(L.a0))
         ldo = (conv.out_channels + 3) // 4 * 4
         n, c, h, w = L.shape
         buf = torch.empty((n, h, w, ldo), dtype=L.a0.dtype, device=L.a0.device)
-        _run_pointwise(L, wp, conv.out_channels, None, b, ACT_NONE, out=buf, ldo=ldo)
+        ops.conv_unit("pw", L, wp, conv.out_channels, None, b, ACT_NONE, out=buf, ldo=ldo)
         return buf, ldo                                         # [n, h, w, ldo] rows, first na*no columns valid
+
+    def _launch_level(self, st, i, xi, nat, level_fn, tail_fn, *dst):
+        """level i from feature map xi into dst: ONE launch (level_fn: ops.detect_level / detect_level_aug, csrc/ly_detect.hip) when the map
+        is a plain tensor of a shape the kernel is built for, else the head GEMM + tail_fn (ops.detect_tail / detect_tail_aug)"""
+        conv = self.m[i]
+        ny, nx = st["hw"][i]
+        fused = None
+        if isinstance(xi, torch.Tensor) and xi.dim() == 4 and conv.bias is not None:
+            fused = ops.detect_level_rows(xi, conv.in_channels, self.na, self.no)
+        if fused is not None:
+            wp, b = self._packed_nat(i, ops.planes_of(xi)) if nat else self._packed(i, ops.planes_of(xi))
+            level_fn(fused[0], fused[1], st["bs"], ny, nx, conv.in_channels, wp, b, self.na, self.no, self.anchors[i], self._strides()[i], *dst,
+                     nat=nat)
+        else:
+            buf, ldo = self._head(i, xi)
+            tail_fn(buf, ldo, st["bs"], ny, nx, self.na, self.no, self.anchors[i], self._strides()[i], *dst)
 
     def _strides(self):
         key = (self.stride.data_ptr(), self.stride._version)
@@ -1081,46 +998,24 @@ class Detect(nn.Module):
             st["forked"] = True
             ctx.__enter__()
         try:
-            ny, nx = st["hw"][i]
             aug = st.get("descale")
-            if aug is not None:                             # augmented pass: descaled rows only
-                self._level_aug(st, i, xi, ny, nx, aug)
+            if aug is not None:                             # augmented pass: descaled rows only (ly_detect_level_aug / ly_detect_tail_aug)
+                if st["offs"][i] is None:
+                    raise ValueError(f"Detect level {i} is not among the levels {st['levels']} this pass writes")
+                self._launch_level(st, i, xi, True, ops.detect_level_aug, ops.detect_tail_aug, st["z"], st["zrows"], st["offs"][i], *aug)
                 return
+            ny, nx = st["hw"][i]
             ext = getattr(self, "_out", None)
             p = ext["p"][i] if ext is not None else torch.empty((st["bs"], self.na, ny, nx, self.no), dtype=torch.float32, device=st["device"])
-            fused = self._fused_level_input(i, xi)
-            if fused is not None:                           # head convolution + decode in one launch (csrc/ly_detect.hip)
-                # train mode (raw maps only, grad disabled): the weight image grad.DetectHeadFn contracts with, so that the maps are bit
-                # for bit those of the recording forward (the natural-k image sums the products of a k-step in another order)
-                nat = not self.training
-                wp, b = self._packed_nat(i, ops.planes_of(xi)) if nat else self._packed(i, ops.planes_of(xi))
-                ops.detect_level(fused[0], fused[1], st["bs"], ny, nx, self.m[i].in_channels, wp, b, self.na, self.no, self.anchors[i],
-                                 self._strides()[i], p, st["z"], st["zrows"], st["offs"][i], nat=nat)
-            else:
-                buf, ldo = self._head(i, xi)
-                ops.detect_tail(buf, ldo, st["bs"], ny, nx, self.na, self.no, self.anchors[i], self._strides()[i], p, st["z"], st["zrows"],
-                                st["offs"][i])
+            # train mode (raw maps only, grad disabled): the weight image grad.DetectHeadFn contracts with, so that the maps are bit for bit
+            # those of the recording forward (the natural-k image sums the products of a k-step in another order)
+            self._launch_level(st, i, xi, not self.training, ops.detect_level, ops.detect_tail, p, st["z"], st["zrows"], st["offs"][i])
             if side:
                 p.record_stream(main)
             st["p"][i] = p
         finally:
             if side:
                 ctx.__exit__(None, None, None)
-
-    def _level_aug(self, st, i, xi, ny, nx, aug):
-        """level i of an augmented pass: ly_detect_level_aug, or the head GEMM + ly_detect_tail_aug where the one-launch kernel is not built"""
-        if st["offs"][i] is None:
-            raise ValueError(f"Detect level {i} is not among the levels {st['levels']} this pass writes")
-        scale, flip, img_w = aug
-        fused = self._fused_level_input(i, xi)
-        if fused is not None:
-            wp, b = self._packed_nat(i, ops.planes_of(xi))
-            ops.detect_level_aug(fused[0], fused[1], st["bs"], ny, nx, self.m[i].in_channels, wp, b, self.na, self.no, self.anchors[i],
-                                 self._strides()[i], st["z"], st["zrows"], st["offs"][i], scale, flip, img_w)
-        else:
-            buf, ldo = self._head(i, xi)
-            ops.detect_tail_aug(buf, ldo, st["bs"], ny, nx, self.na, self.no, self.anchors[i], self._strides()[i], st["z"], st["zrows"],
-                                st["offs"][i], scale, flip, img_w)
 
     def _make_grid(self, nx=20, ny=20, i=0):
         d, t = self.anchors[i].device, self.anchors[i].dtype

@@ -161,10 +161,15 @@ def rows(x):
     if sc == 1 and sw >= c and sw % vw_of(x) == 0 and (h == 1 or sh == w * sw) and (n == 1 or sn == h * w * sw) and w > 1 \
             and x.data_ptr() % 16 == 0:
         return x, sw
+    return rows_dense(x), c
+
+
+def rows_dense(x):
+    """NHWC-dense view of a logical [n, c, h, w] tensor (copy only if needed)."""
     x = nhwc(x)
     if x.stride(1) != 1:        # degenerate shapes where torch reports ambiguous strides
         x = x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    return x, c
+    return x
 
 
 _p = capi.ptr
@@ -238,6 +243,89 @@ def conv3x3(*, M, H, W, Cin, N, x, ldx, wp, out, ldo, e_scale=None, e_shift=None
         name = "ly_conv3x3_lat_kernel<__bf16, 2, 2>"        # conv3_dispatch (csrc/ly_conv3x3.hip): grids under two blocks per CU take the latency form
     with _Timed(name, 2.0 * M * 9 * Cin * N, x.element_size() * M * (Cin + N) + 4.0 * 9 * Cin * N):
         capi.check(capi.lib().ly_conv3x3_fwd(ctypes.byref(P), capi.stream_ptr()), "ly_conv3x3_fwd")
+
+
+class Lazy:
+    """A not-yet-materialised activation a consumer GEMM can absorb: channel concat of up to two row
+    sources, the first optionally at half resolution (nearest 2x upsample) or gated by CoordAtt."""
+
+    def __init__(self, shape, a0, lda0, k0, a1=None, lda1=0, up=False, gate=None, keep=()):
+        self.shape = shape          # logical (n, c, h, w)
+        self.a0, self.lda0, self.k0 = a0, lda0, k0
+        self.a1, self.lda1 = a1, lda1
+        self.up = up
+        self.gate = gate            # (a_h, a_w) or None
+        self.keep = keep            # tensors kept alive
+
+    @staticmethod
+    def of(x, x1=None, up=False):
+        """x itself when it is a Lazy, else the rows of the tensor x [| x1 beside it], x at half resolution when `up`"""
+        if isinstance(x, Lazy):
+            return x
+        t, ld = rows(x)
+        n, c, h, w = t.shape
+        if up:
+            h, w = 2 * h, 2 * w
+        if x1 is None:
+            return Lazy((n, c, h, w), t, ld, c, up=up, keep=(t,))
+        t1, ld1 = rows(x1)
+        return Lazy((n, c + t1.shape[1], h, w), t, ld, c, a1=t1, lda1=ld1, up=up, keep=(t, t1))
+
+    def materialize(self):
+        n, c, h, w = self.shape
+        if self.gate is not None:
+            assert self.a1 is None and not self.up
+            return coordatt_gate(self.a0, self.lda0, n, h, w, c, self.gate[0], self.gate[1])
+        parts = []
+        a0 = self.keep[0]
+        if self.up:
+            a0 = torch.nn.functional.interpolate(a0, scale_factor=2, mode="nearest")
+        parts.append(a0)
+        if self.a1 is not None:
+            parts.append(self.keep[1])
+        return parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+
+
+def sources(x):
+    """(x0, x1, up) of a tensor or Lazy: the tensors autograd sees as the inputs of a training node (Lazy.of(x0, x1, up) is the
+    node's source again).  The nodes carry no gate prologue: a gated Lazy is materialised first."""
+    if not isinstance(x, Lazy):
+        return x, None, False
+    if x.gate is not None:
+        return x.materialize(), None, False
+    return x.keep[0], (x.keep[1] if x.a1 is not None else None), x.up
+
+
+def unit_out(kind, src, n_out, k=1, dtype=None):
+    """fresh NHWC output of conv_unit(kind, src, ..., n_out) (k: the patch size of kind "patch")"""
+    n, _, h, w = src.shape
+    return empty_nhwc(n, n_out, h // k, w // k, src.a0 if isinstance(src, Lazy) else src, dtype)
+
+
+def conv_unit(kind, src, wp, n_out, e_scale, e_shift, act, *, stats=None, out=None, ldo=None, k=1, nchw=False, dtype=None):
+    """THE forward launch of a conv -> [BN] -> act unit, eval and training: out rows (stride ldo, default n_out) = act(e_scale * conv(src; wp)
+    + e_shift), and / or its per-channel statistics.  kind "pw": 1x1 over a Lazy (one or two row sources, 2x-upsample gather, CoordAtt gate
+    prologue); "c3": 3x3 stride 1 pad 1 over a tensor; "patch": k x k stride k over an NHWC tensor, or (nchw) over an NCHW image.  dtype: the
+    storage type of the patch output when it is not the source's (an fp32 / uint8 image -> a bf16 map)."""
+    ep = dict(N=n_out, wp=wp, out=out, ldo=n_out if ldo is None else ldo, e_scale=e_scale, e_shift=e_shift, act=act, stats=stats)
+    if kind == "pw":
+        n, c, h, w = src.shape
+        pro = dict(pro=PRO_GATE, g_h=src.gate[0], g_w=src.gate[1]) if src.gate is not None else {}
+        gemm(M=n * h * w, H=h, W=w, K=c, a0=src.a0, lda0=src.lda0, k0=src.k0, a1=src.a1, lda1=src.lda1,
+             gather=GATHER_UP2 if src.up else GATHER_ROWS, **pro, **ep)
+    elif kind == "c3":
+        x, ld = rows(src)
+        n, c, h, w = x.shape
+        conv3x3(M=n * h * w, H=h, W=w, Cin=c, x=x, ldx=ld, **ep)
+    else:
+        n, c, h, w = src.shape
+        if nchw:
+            if k != 4 or w % 4 != 0:
+                raise NotImplementedError("HIP patch embedding of an NCHW image needs patch_size 4 and W % 4 == 0")
+            g = dict(K=16 * c, a0=src.contiguous(), lda0=0, k0=16 * c, gather=GATHER_PATCH_NCHW, ks=4, pk=0)
+        else:                                           # the patch gather walks dense rows (lda0 = c): a channel slice is copied
+            g = dict(K=k * k * c, a0=rows_dense(src), lda0=c, k0=k * k * c, gather=GATHER_PATCH, ks=k, pk=k * c)
+        gemm(M=n * (h // k) * (w // k), H=h // k, W=w // k, Hin=h, Win=w, Cin=c, dtype=dtype or g["a0"].dtype, **g, **ep)
 
 
 def _tname(t):
@@ -526,6 +614,18 @@ def detect_tail(y, ldy, n, h, w, na, no, anchors, stride, p, z, zrows, zoff):
 
 def detect_level_ok(k, na, no, dtype):
     return dtype in (torch.float32, torch.bfloat16) and bool(capi.lib().ly_detect_level_ok(k, na, no, capi.dtype_code(dtype)))
+
+
+FUSED_DETECT_LEVEL = True      # development switch: False sends Detect levels, eval and training, through the GEMM + ly_detect_tail pair
+                               # (training forward: measured 25-50 us per step slower)
+
+
+def detect_level_rows(x, cin, na, no):
+    """the feature map x as (rows, ld) when the one-launch level kernel (detect_level / detect_level_aug) takes it, else None"""
+    if not FUSED_DETECT_LEVEL or not detect_level_ok(cin, na, no, x.dtype):
+        return None
+    t, ld = rows(x)
+    return (t, ld) if ld % vw_of(t) == 0 and t.data_ptr() % 16 == 0 else None
 
 
 def detect_level(x, ldx, n, h, w, k, wp, bias, na, no, anchors, stride, p, z, zrows, zoff, nat=True):

@@ -631,7 +631,6 @@ def test_detect_level_one_launch_matches_gemm_plus_tail(dt):
     same z / raw maps.  bf16 storage: the pair now contracts the widened map in fp32 storage with the unrounded fp32 weights (bf16x3), the
     one-launch kernel with single-plane bf16 weights: the two differ by the bf16 rounding of the weights, which the 2e-2 band covers"""
     import lead_yolo_amd as L
-    from lead_yolo_amd import modules
     dev = _dev()
     torch.manual_seed(5)
     ch = (64, 128, 256) if dt == torch.float32 else (128, 256, 512)
@@ -641,11 +640,11 @@ def test_detect_level_one_launch_matches_gemm_plus_tail(dt):
     xs = [torch.randn(3, c, s, s + 1, device=dev).to(dt).contiguous(memory_format=torch.channels_last) for c, s in zip(ch, (20, 10, 5))]
     with torch.no_grad():
         z1, p1 = det([t for t in xs])
-        modules.FUSED_DETECT_LEVEL = False
+        L.ops.FUSED_DETECT_LEVEL = False
         try:
             z0, p0 = det([t for t in xs])
         finally:
-            modules.FUSED_DETECT_LEVEL = True
+            L.ops.FUSED_DETECT_LEVEL = True
     tol = dict(rtol=2e-2, atol=2e-2) if dt == torch.bfloat16 else dict(rtol=1e-4, atol=1e-4)
     assert z1.shape == z0.shape == (3, 3 * (20 * 21 + 10 * 11 + 5 * 6), 6)
     for a, b in zip(p1, p0):
