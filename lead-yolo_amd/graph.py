@@ -23,9 +23,21 @@ def _pick_parts(bs, dtype=torch.float32):
     return 1
 
 
+def fingerprint(model):
+    """what GraphedForward.stale() compares: address, dtype and version counter of every state_dict tensor, and pack.EPOCH (which
+    pack.touch_weights() and every raw-pointer writer of the package move)"""
+    from . import pack
+    sd = model.state_dict()
+    return tuple(sd), tuple(t.dtype for t in sd.values()), pack.versions(*sd.values())
+
+
 class GraphedForward:
     """g = GraphedForward(model, example);  (z, [p3, p4, p5]) = g(x)  replays the captured forward on x (same shape / dtype as
     example).  The returned tensors are the graph's static outputs: consume or copy them before the next call.
+    Replays do NOT follow weight changes: the graph holds the addresses of the packed weight images and folded BatchNorm tables the
+    modules had prepared when it was captured; after the weights change the modules prepare new tables and the replay keeps reading the old
+    ones.  `stale()` tells (it is not called by a replay: polling some 400 version counters would cost a good part of a 1.5 ms forward);
+    when it returns True, build a new GraphedForward.
     augment=True captures the augmented inference forward instead, (z, None) = g(x): the resampling launch, then its three passes on three
     streams (the passes replace the sub-batches: `parts` is 1 and the per-layer forks stay off), joined before z is read."""
 
@@ -40,6 +52,7 @@ class GraphedForward:
                 raise ValueError("augment=True runs its passes side by side: parts must be 1")
             self.parts = 1
             self._capture_augmented(model, warmup, example)
+            self._fingerprint = fingerprint(model)
             return
         bs = example.shape[0]
         self.parts = parts = _pick_parts(bs, example.dtype) if parts is None else parts
@@ -54,6 +67,15 @@ class GraphedForward:
             self._warm_and_capture(model, xs, parts, cur, warmup, example)
         finally:
             ops.CONCURRENT_PARTS = keep_parts
+        self._fingerprint = fingerprint(model)
+
+    def stale(self):
+        """True when the model's weights may have changed since the capture — a version counter, an address or a dtype of a state_dict
+        tensor moved, or pack.touch_weights() / a raw-pointer writer of this package (fused optimiser, train-mode forward, replayed training
+        graph — of ANY model in the process: the epoch is global, so this errs on the side of True) ran.  The replays then still compute
+        with the weights of the capture: build a new GraphedForward.  A write through `.data` that was not followed by
+        pack.touch_weights() is invisible here as everywhere."""
+        return fingerprint(self.model) != self._fingerprint
 
     def _warm_and_capture(self, model, xs, parts, cur, warmup, example):
         with torch.no_grad():

@@ -55,6 +55,20 @@ class _Prepared:
         self.slots = {}
 
 
+class _Holder(nn.Module):
+    """base of the modules that keep prepared copies of their parameters.  `.to()` / `.float()` / `.half()` / `.bfloat16()` give every
+    parameter new storage WITHOUT moving its version counter, and the allocator may hand a later conversion the address an earlier one
+    freed: after `.bfloat16().float()` a weight can sit at its old address with its old version and bf16-rounded values.  No key built
+    from (address, version) can see that — a dtype in the key would not either, the round trip ends in the dtype it began in — so the
+    conversion announces itself.  Every holder does (any of them can be the root of the conversion; inside `model.to()` that is two
+    integer increments per holder), and the epoch is process-wide: every model prepares its tables again at its next forward."""
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        pack.touch_weights()
+        return out
+
+
 def _edge(fn):
     """forward wrapper applying the dtype policy of ops.edge_in / edge_out around a module's body, and running the body with
     autocast OFF: inside a module every dtype is explicit (storage dtype activations, fp32 tables), torch helper ops on pooled
@@ -147,7 +161,7 @@ class Partial_conv3(nn.Module):
         self.partial_conv3.weight._ly_tap_major = True
 
 
-class MLPBlock(nn.Module):
+class MLPBlock(_Holder):
     """x + W2 . relu(BN(W1 . [pconv3x3(x[:, :C/4]) | x[:, C/4:]]))  as ONE fused HIP kernel."""
 
     def __init__(self, dim, n_div=4, mlp_ratio=2, drop_path=0.0, layer_scale_init_value=0, act_layer=nn.ReLU,
@@ -251,7 +265,7 @@ class BasicStage(nn.Module):
         return x
 
 
-class _PatchConv(nn.Module):
+class _PatchConv(_Holder):
     """k x k stride-k convolution (no bias) + BatchNorm as one gather-GEMM."""
     _conv_name = "proj"
     stride_factor = None
@@ -356,7 +370,7 @@ def autopad(k, p=None, d=1):
     return p
 
 
-class Conv(nn.Module):
+class Conv(_Holder):
     default_act = nn.SiLU()
 
     def __init__(self, c1, c2, k=1, s=1, p=None, g=1, d=1, act=True):
@@ -445,7 +459,7 @@ class SE(nn.Module):
         return self.attention(xr, ld, n, h * w, c).view(n, c, 1, 1)
 
 
-class RFCBAMConv(nn.Module):
+class RFCBAMConv(_Holder):
     def __init__(self, in_channel, out_channel, kernel_size=3, stride=1, dilation=1):
         super().__init__()
         k = kernel_size
@@ -604,7 +618,7 @@ class h_swish(nn.Module):
         self.sigmoid = h_sigmoid(inplace=inplace)
 
 
-class CoordAtt(nn.Module):
+class CoordAtt(_Holder):
     def __init__(self, inp, oup, reduction=32):
         super().__init__()
         if inp != oup:
@@ -705,7 +719,7 @@ class CA_Bottleneck(nn.Module):
         return y.materialize() if isinstance(y, Lazy) else y
 
 
-class C3_CA(nn.Module):
+class C3_CA(_Holder):
     def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
         super().__init__()
         c_ = int(c2 * e)
@@ -858,7 +872,7 @@ class Concat(nn.Module):
         return torch.cat(x, self.d)
 
 
-class Detect(nn.Module):
+class Detect(_Holder):
     stride = None
     dynamic = False
     export = False
@@ -911,6 +925,11 @@ class Detect(nn.Module):
         ops.conv_unit("pw", L, wp, conv.out_channels, None, b, ACT_NONE, out=buf, ldo=ldo)
         return buf, ldo                                         # [n, h, w, ldo] rows, first na*no columns valid
 
+    def _anchors_f32(self, i):
+        """level i's anchors as the float32 the decode kernels read (`model.half()` / `.bfloat16()` converts the buffer with the parameters)"""
+        a = self.anchors[i]
+        return a if a.dtype == torch.float32 else a.float()
+
     def _launch_level(self, st, i, xi, nat, level_fn, tail_fn, *dst):
         """level i from feature map xi into dst: ONE launch (level_fn: ops.detect_level / detect_level_aug, csrc/ly_detect.hip) when the map
         is a plain tensor of a shape the kernel is built for, else the head GEMM + tail_fn (ops.detect_tail / detect_tail_aug)"""
@@ -921,11 +940,11 @@ class Detect(nn.Module):
             fused = ops.detect_level_rows(xi, conv.in_channels, self.na, self.no)
         if fused is not None:
             wp, b = self._packed_nat(i, ops.planes_of(xi)) if nat else self._packed(i, ops.planes_of(xi))
-            level_fn(fused[0], fused[1], st["bs"], ny, nx, conv.in_channels, wp, b, self.na, self.no, self.anchors[i], self._strides()[i], *dst,
+            level_fn(fused[0], fused[1], st["bs"], ny, nx, conv.in_channels, wp, b, self.na, self.no, self._anchors_f32(i), self._strides()[i], *dst,
                      nat=nat)
         else:
             buf, ldo = self._head(i, xi)
-            tail_fn(buf, ldo, st["bs"], ny, nx, self.na, self.no, self.anchors[i], self._strides()[i], *dst)
+            tail_fn(buf, ldo, st["bs"], ny, nx, self.na, self.no, self._anchors_f32(i), self._strides()[i], *dst)
 
     def _strides(self):
         key = (self.stride.data_ptr(), self.stride._version)

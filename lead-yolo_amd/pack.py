@@ -212,7 +212,9 @@ W_EPOCH = 0
 
 
 def touch_weights():
-    """weights were written through raw pointers (fused optimiser step, replayed graph): packed images must be refreshed"""
+    """weights were written behind torch's version counters — through raw pointers (fused optimiser step, replayed graph) or through
+    `.data` (`p.data.mul_(2)` leaves `p._version` where it was): packed images, folded tables and float32 shadows must be refreshed.
+    The contract for callers: every such write is followed by this call before the next forward."""
     global W_EPOCH
     W_EPOCH += 1
     touch()
@@ -223,14 +225,16 @@ _SHADOW = {}
 
 def master(param):
     """the contiguous float32 tensor the packer reads: the parameter itself, or — for `.half()` / `.bfloat16()` models (inference) — a
-    cached float32 copy, rebuilt when the parameter changes"""
+    cached float32 copy, rebuilt when the parameter changes: its version counter moved, or `touch_weights()` announced a write that
+    moves no counter (`.data`, raw pointers)"""
     if param.dtype == torch.float32 and param.is_contiguous():
         return param
     ent = _SHADOW.get(id(param))
-    if ent is None or ent[0]() is not param or ent[1] != param._version:
+    key = (param._version, W_EPOCH, param.data_ptr())
+    if ent is None or ent[0]() is not param or ent[1] != key:
         sh = param.detach().float().contiguous()
         ref = weakref.ref(param, lambda _r, k=id(param): _SHADOW.pop(k, None))
-        _SHADOW[id(param)] = ent = (ref, param._version, sh)
+        _SHADOW[id(param)] = ent = (ref, key, sh)
     return ent[2]
 
 
@@ -254,6 +258,9 @@ class Src:
     @property
     def param(self):
         p = self._ref()
+        if p is not None and p.data_ptr() != self.ptr:
+            return None                            # the tensor lives on but its storage moved (`.to()`, `.float()`, `p.data = ...`): this
+                                                   # description addresses memory it no longer owns, and counts as dead
         if self._ref2 is None or p is None:
             return p
         q = self._ref2()
