@@ -422,6 +422,43 @@ int ly_val_match(const float* dets, const int* counts, int bs, int max_det, cons
                  float* cls, int* match_label, float* match_iou, int* n_det, int* nt_class, int* overflow, void* stream);
 int ly_val_advance(int* cursor, int bs, void* stream);
 
+/* ---- detect input path on the device (csrc/ly_letterbox.hip; detect.py, utils/dataloaders.py LoadImages.__next__ / load_image) -----------
+ * A LyLetterboxImage describes one output canvas: the source picture (as cv2.imread or a decoder hands it over) resized to nh x nw, placed
+ * with its corner at (top, left), 114 everywhere else.  The host computes nh, nw, top, left with letterbox's own arithmetic
+ * (lead-yolo_amd/predict.py letterbox_plan); a slot without a picture (an all-114 canvas) has nh = nw = 0.                                 */
+typedef struct LyLetterboxImage {
+  const unsigned char* src; /* device: h0 x w0 x 3 uint8, HWC BGR, rows packed                                  */
+  unsigned char* dst;     /* device: this entry's output canvas                                               */
+  int h0, w0;             /* source size                                                                      */
+  int H, W;               /* canvas size                                                                      */
+  int nh, nw;             /* resized picture (letterbox's new_unpad), 1 <= nh <= H - top, 1 <= nw <= W - left */
+  int top, left;          /* picture's corner on the canvas; everything else = 114                            */
+} LyLetterboxImage;
+enum { LY_LB_CHW_RGB = 0, LY_LB_HWC_BGR = 1 };
+/* One launch for a batch of canvases.  Replaces utils/augmentations.py letterbox (cv2.resize INTER_LINEAR + cv2.copyMakeBorder(114)) and
+ * the transpose((2, 0, 1))[::-1] of utils/dataloaders.py LoadImages.__next__ (layout LY_LB_CHW_RGB: dst = three planes R, G, B of H * W
+ * bytes, the model's uint8 NCHW input; W a multiple of 16 and dst 16-byte aligned), and the cv2.resize of load_image (layout LY_LB_HWC_BGR:
+ * dst = packed H x W x 3, the form the image bank holds; any W, any alignment).  imgs: DEVICE table of n_img entries; maxH, maxW: the
+ * largest H and W of the table (the grid).
+ * Pixel contract — OpenCV's 8-bit INTER_LINEAR written out in integers.  Canvas pixel (v, u) outside [top, top + nh) x [left, left + nw):
+ * 114.  (nh, nw) == (h0, w0): the source pixel (letterbox skips cv2.resize).  Otherwise, with dx = u - left:
+ *   scale = 1.0 / ((double)nw / w0);  fx = (float)((dx + 0.5) * scale - 0.5);  sx = floor(fx);  fx -= sx;
+ *   sx < 0: sx = 0, fx = 0;   sx >= w0 - 1: sx = w0 - 1, fx = 0;
+ *   a1 = rint(fx * 2048.f), a0 = rint((1.f - fx) * 2048.f)  (half to even);  taps at x0 = sx and x1 = min(sx + 1, w0 - 1);
+ * the same in y gives sy, b0, b1 and the rows y0, y1;  per channel in int32  r_k = S[y_k][x0] * a0 + S[y_k][x1] * a1  and
+ *   out = (((b0 * (r_0 >> 4)) >> 16) + ((b1 * (r_1 >> 4)) >> 16) + 2) >> 2.
+ * An exact 2:1 reduction gives the rounded 2 x 2 mean (what cv2.resize's switch to INTER_AREA produces there).  The build machine has no
+ * cv2: what the tests hold the kernel to is bit-equality with this contract restated in numpy (tests/test_gpu_letterbox.py), and that
+ * restatement to float64 half-pixel bilinear within one grey level.                                                                        */
+int ly_letterbox_u8(const LyLetterboxImage* imgs, int n_img, int maxH, int maxW, int layout, void* stream);
+/* Boxes of the letterboxed batch in the pixels of the original images: utils/general.py scale_boxes + clip_boxes (detect.py:
+ * `det[:, :4] = scale_boxes(im.shape[2:], det[:, :4], im0.shape).round()`) for what nms_padded returns, one thread per (image, row).
+ * dets [bs, max_det, 6] / counts [bs];  shapes [bs, 5] = (h0, w0, gain, padw, padh).  Rows < counts[b]: x1, x2 -> clamp((x - padw) / gain,
+ * 0, w0), y1, y2 -> clamp((y - padh) / gain, 0, h0) in fp32, in that order of operations, then rintf (torch.round) when round_boxes != 0;
+ * conf and cls copied.  Rows >= counts[b] are written as zeros.  out [bs, max_det, 6] may alias dets.                                     */
+int ly_scale_boxes(const float* dets, const int* counts, int bs, int max_det, const float* shapes, int round_boxes, float* out,
+                   void* stream);
+
 /* ---- backward building blocks of the training step (train.py:324 `scaler.scale(loss).backward()`) -------------
  * Data gradients of 1x1 / 3x3 stride-1 convolutions reuse ly_gemm_fwd / ly_conv3x3_fwd with transposed weights.   */
 

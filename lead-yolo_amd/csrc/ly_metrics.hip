@@ -24,6 +24,7 @@
 // order, so IoUs are bit-equal to the reference's and the `>= level` decisions are the same.
 #include <limits.h>
 
+#include "ly_boxes.hpp"                 // ly_val_native: scale_boxes with ratio_pad + clip_boxes
 #include "ly_common.hpp"
 #include "ly_params.h"
 
@@ -32,12 +33,6 @@
 #define LY_VAL_OVF_CLASS 2
 
 static_assert(LY_VAL_MAX_LABELS >= 512 && LY_VAL_MAX_LABELS * (LY_VAL_LEVELS + 6) * 4 + 64 <= 65536, "labels + first[][] must fit static LDS");
-
-// scale_boxes with ratio_pad + clip_boxes (utils/general.py:800-829): (x - pad) / gain, clamped to the native image
-__device__ __forceinline__ float ly_val_native(float v, float pad, float gain, float hi) {
-  v = (v - pad) / gain;
-  return v < 0.f ? 0.f : (v > hi ? hi : v);
-}
 
 __global__ __launch_bounds__(LY_THREADS) void ly_val_match_kernel(const float* __restrict__ dets, const int* __restrict__ counts, int max_det,
                                                                   const float* __restrict__ targets, long nt, float W, float H,

@@ -2,7 +2,8 @@
 load_mosaic (or letterbox), random_perspective, augment_hsv, flipud / fliplr, HWC BGR -> CHW RGB, and the label rows — as two HIP launches per
 batch (csrc/ly_mosaic.hip) that write the uint8 NCHW batch and the fixed-shape padded `targets` the training step reads.
 
-    bank = ImageBank.from_dataset(ds)                  # or ImageBank(images, labels, img_size): load_image results, decoded once
+    bank = ImageBank.from_dataset(ds)                  # or ImageBank(images, labels, img_size): load_image results, decoded once;
+                                                       # or ImageBank.from_native(images, labels, img_size): decoded images, resized on the device
     aug = MosaicAugment(bank, hyp, batch_size=64, seed=0)
     imgs, targets = aug(next_indices)                  # (uint8 [bs, 3, s, s], float32 [aug.capacity, 6]); no host sync
     aug(next_indices, out=(step.imgs, step.targets))   # straight into a GraphedTrainStep's captured buffers; then step()
@@ -51,6 +52,9 @@ class ImageBank:
         self.hw = np.array(hw, dtype=np.int64).reshape(-1, 2)
         self.off = np.array(offs, dtype=np.int64)
         self.data = torch.from_numpy(np.concatenate(flat)).to(self.device)
+        self._set_labels(labels)
+
+    def _set_labels(self, labels):
         labs, lab_off, nlab, r = [], [], [], 0
         for i, lb in enumerate(labels):
             a = np.asarray(lb.cpu().numpy() if isinstance(lb, torch.Tensor) else lb, dtype=np.float64).reshape(-1, 5) if len(lb) else np.zeros((0, 5))
@@ -69,6 +73,43 @@ class ImageBank:
         """a reference LoadImagesAndLabels (duck-typed: len(), load_image(i) -> (im, hw0, hw), .labels, .img_size): every image decoded and
         resized once, as its `--cache ram` does"""
         return cls([ds.load_image(i)[0] for i in range(len(ds))], ds.labels, ds.img_size, bgr=True, device=device)
+
+    @classmethod
+    def from_native(cls, images, labels, img_size, device=None):
+        """`load_image` on the device: images as decoded (uint8 HWC BGR of any sizes; numpy arrays, CPU tensors or contiguous device tensors),
+        each resized so that its long side is img_size — r = img_size / max(h0, w0), size (int(w0 * r), int(h0 * r)), truncated as
+        load_image does — by one ly_letterbox_u8 launch (layout HWC BGR) straight into the bank buffer.  The interpolation is always
+        INTER_LINEAR, which is what load_image uses for the augment=True loader this bank feeds (it takes INTER_AREA only for a
+        non-augmenting loader that shrinks); an image whose long side is img_size already is copied."""
+        from . import predict
+        if len(images) == 0 or len(images) != len(labels):
+            raise ValueError(f"ImageBank: {len(images)} images and {len(labels)} label arrays (need the same, non-zero count)")
+        self = cls.__new__(cls)
+        self.img_size = int(img_size)
+        self.device = predict._device(device)
+        src, keep = predict._sources(images, self.device, "ImageBank.from_native")
+        n = len(src)
+        table = (capi.LyLetterboxImage * n)()
+        hw, offs, off = [], [], 0
+        for i, (_, h0, w0) in enumerate(src):
+            r = self.img_size / max(h0, w0)
+            nh, nw = int(h0 * r), int(w0 * r)
+            if nh < 1 or nw < 1:
+                raise ValueError(f"ImageBank.from_native: image {i} ({h0} x {w0}) would be resized to {nh} x {nw}")
+            hw.append((nh, nw))
+            offs.append(off)
+            off += nh * nw * 3
+        self.hw = np.array(hw, dtype=np.int64).reshape(-1, 2)
+        self.off = np.array(offs, dtype=np.int64)
+        self.data = torch.empty(off, dtype=torch.uint8, device=self.device)
+        for i, (p, h0, w0) in enumerate(src):
+            nh, nw = hw[i]
+            table[i] = capi.LyLetterboxImage(p, self.data.data_ptr() + offs[i], h0, w0, nh, nw, nh, nw, 0, 0)
+        table_dev, _ = predict._upload(table, np.zeros(0, dtype=np.float32), self.device)
+        predict._launch(table_dev, n, int(self.hw[:, 0].max()), int(self.hw[:, 1].max()), predict.LB_HWC_BGR)
+        del keep
+        self._set_labels(labels)
+        return self
 
     def __len__(self):
         return len(self.hw)
