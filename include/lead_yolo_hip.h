@@ -421,6 +421,18 @@ int ly_val_match(const float* dets, const int* counts, int bs, int max_det, cons
                  const float* levels, int single_cls, int nc, const int* cursor, int capacity, int row_width, void* correct, float* conf,
                  float* cls, int* match_label, float* match_iou, int* n_det, int* nt_class, int* overflow, void* stream);
 int ly_val_advance(int* cursor, int bs, void* stream);
+/* ly_val_confusion replaces ConfusionMatrix.process_batch (utils/metrics.py `class ConfusionMatrix`, called by val.py's `run` per image that has
+ * labels; conf 0.25 and IoU 0.45 are the class's defaults) for a whole batch: one launch, one block per image, the same inputs as ly_val_match.
+ *   matrix [(nc + 1) * (nc + 1)] int32: row = predicted class, column = true class, index nc = background; every launch ADDS to it (no
+ *   cursor: a captured launch replays batch after batch).  Over the detections with conf > conf_thres: a detection's label is the label of
+ *   any class with the largest IoU > iou_thres (lowest targets row on equal IoU); a label's detection is the one with the largest IoU among
+ *   those (lowest index on equal IoU).  A label with a detection adds 1 to matrix[cls(det)][cls(label)], one without to matrix[nc][cls(label)];
+ *   a kept detection that did not get its label adds 1 to matrix[cls(det)][nc] — only in an image with at least one matched pair, as the
+ *   reference's `if n:` has it.  An image without labels adds nothing.  single_cls != 0: prediction class 0.
+ *   flags[0] is OR-ed with the bits of ly_val_match's overflow: bit 0 an image with more than LY_VAL_MAX_LABELS labels (the image is
+ *   skipped), bit 1 a label or kept-detection class outside [0, nc) (that row is not counted).  max_det <= 16384.                           */
+int ly_val_confusion(const float* dets, const int* counts, int bs, int max_det, const float* targets, long nt, int W, int H,
+                     const float* shapes, float conf_thres, float iou_thres, int single_cls, int nc, int* matrix, int* flags, void* stream);
 
 /* ---- detect input path on the device (csrc/ly_letterbox.hip; detect.py, utils/dataloaders.py LoadImages.__next__ / load_image) -----------
  * A LyLetterboxImage describes one output canvas: the source picture (as cv2.imread or a decoder hands it over) resized to nh x nw, placed
@@ -696,18 +708,20 @@ int ly_rf3s_bwd(const LyRf1BwdParams* p, int Ho, int Wo, int pass, void* stream)
  *   p / dp   [bs][na][ny][nx][no] predictions / their gradient (dp zeroed by the caller; d(total loss)/dp on return)
  *   anchors  [na][2] in grid units (Detect.anchors[i]);  targets [nt][6] = (image, class, x, y, w, h) normalised
  *   tobj [cells] zeroed, winner [cells] filled with -1, cand_cell [5*na*nt], cand [5*na*nt][5] workspaces
- *   acc [8] zeroed: sum(1 - eiou), matches, sum of objectness BCE, rejected target rows, sum of class BCE, 3 unused  -> ly_loss_finish
+ *   acc [16] zeroed, 8-byte aligned -> ly_loss_finish: three int64 sums in 2^-30 fixed point (1 - eiou, objectness BCE, class BCE: integer
+ *   atomics, so the loss does not depend on the order the blocks arrive in), matches [6], rejected target rows [7], and three float slots
+ *   [8..10] for terms fixed point does not take (non-finite, or 2^20 and more)
  *   tbox     NULL or [5*na*nt][4]: (gx - gi, gy - gj, gw, gh) of every valid candidate (build_targets' `tbox`, utils/loss.py:262)
  *   match_only != 0: target assignment only (utils/loss.py:194-268 build_targets): cand_cell[idx] = flattened cell
  *            ((b*na + a)*ny + gj)*nx + gi of candidate idx = (k*na + a)*nt + t, or -1; tbox as above; p is read, dp/tobj untouched.
  * A target row whose image index is exactly -1 is padding and is ignored (fixed-shape target buffers of a captured step).
- * A target row whose image index is outside [0, bs) or that holds a NaN is rejected and counted in acc[3] (the torch
+ * A target row whose image index is outside [0, bs) or that holds a NaN is rejected and counted in acc[7] (the torch
  * formulation raises IndexError there); ly_loss_finish then returns a NaN total.                                          */
 int ly_loss_level(const float* p, float* dp, const float* anchors, const float* targets, int bs, int na, int ny, int nx, int no, long nt,
                   float anchor_t, float box_gain, float obj_gain, float balance, float* tobj, int* winner, long* cand_cell, float* cand,
                   float* acc, float* tbox, int match_only, float cls_gain, float cp, float cn, float cls_pw, float obj_pw, void* stream);
 /* out[0] = (lbox + lobj + lcls) * bs (NaN if any level rejected a target row), out[1] = lbox, out[2] = lobj, out[3] = lcls (0 for nc == 1)
- * from acc [nl][8]; cells / balance: [nl] floats                                                                           */
+ * from acc [nl][16]; cells / balance: [nl] floats                                                                           */
 int ly_loss_finish(const float* acc, int nl, const float* cells, const float* balance, float box_gain, float obj_gain, float cls_gain, int nc,
                    int bs, float* out, void* stream);
 

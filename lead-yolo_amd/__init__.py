@@ -12,5 +12,6 @@ from .optim import FusedAdam, FusedAdamW, FusedSGD  # noqa: F401
 from .graph import GraphedForward  # noqa: F401
 from .nms import nms_padded, non_max_suppression  # noqa: F401,E402
 from .mosaic import ImageBank, MosaicAugment  # noqa: F401,E402
-from .metrics import MatchAccumulator, Validator, ValResult, ap_per_class, compute_ap, match_padded, unpack_correct  # noqa: F401,E402
-from .predict import Detector, LetterboxPlan, letterbox, letterbox_plan, scale_boxes  # noqa: F401,E402
+from .metrics import ConfusionMatrix, MatchAccumulator, Validator, ValResult, ap_per_class, compute_ap, match_padded, unpack_correct  # noqa: F401,E402
+from .predict import Detector, LetterboxPlan, letterbox, letterbox_plan, load_image_size, scale_boxes  # noqa: F401,E402
+from .valrun import ValPlan, ValRun, ValSet, val_labels, val_plan, validate  # noqa: F401,E402

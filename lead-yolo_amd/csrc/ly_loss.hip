@@ -16,7 +16,29 @@
 //   ly_loss_obj     per cell: BCE-with-logits against tobj, its gradient into dpred[..., 4], level sum by block reduction.
 // ly_loss_finish combines the level accumulators into (loss, lbox, lobj, lcls) exactly as the reference does (mean per level,
 // balance [4, 1, 0.4], * hyp gains, * batch size).
+//
+// The three loss sums of a level are ORDER-INDEPENDENT: every term (a candidate's 1 - eiou and class BCE, a block's objectness partial — itself
+// a fixed-order sum) is converted to 2^-30 fixed point on its own and added with a 64-bit INTEGER atomic, so two runs on the same inputs give the
+// same bits whatever order the blocks arrive in (float atomics gave the last bit of lbox / lobj to the scheduler).  The count and the rejected
+// rows are float sums of 1.0, exact below 2^24.  A term that is not finite, or is 2^20 or more, goes to a float slot as it is (a NaN or an Inf
+// still reaches the loss); fixed point holds 2^33 / (term size) terms, far beyond any batch.
 #include "ly_common.hpp"
+
+#define LY_LOSS_ACC 16             // floats per level accumulator, 8-byte aligned: [0,1] [2,3] [4,5] int64 fixed-point sums of 1 - eiou, objectness
+                                   // BCE, class BCE; [6] matches; [7] rejected target rows; [8] [9] [10] the same three sums' terms that fixed
+                                   // point does not take (non-finite or >= 2^20), as floats; the rest unused
+enum { LY_LOSS_BOX = 0, LY_LOSS_OBJ = 1, LY_LOSS_CLS = 2, LY_LOSS_COUNT = 6, LY_LOSS_BAD = 7, LY_LOSS_WILD = 8 };
+#define LY_LOSS_FIX 1073741824.0   // 2^30
+
+__device__ __forceinline__ void ly_loss_add(float* acc, int which, float v) {
+  if (fabsf(v) < 1048576.f)        // false for a NaN
+    atomicAdd(reinterpret_cast<unsigned long long*>(acc) + which, (unsigned long long)(long long)((double)v * LY_LOSS_FIX));
+  else
+    atomicAdd(acc + LY_LOSS_WILD + which, v);
+}
+__device__ __forceinline__ float ly_loss_sum(const float* acc, int which) {
+  return (float)((double)reinterpret_cast<const long long*>(acc)[which] * (1.0 / LY_LOSS_FIX)) + acc[LY_LOSS_WILD + which];
+}
 
 struct D4 {                        // value + derivatives w.r.t. (px, py, pw, ph)
   float v, d[4];
@@ -67,7 +89,7 @@ struct LyLossLevel {
   int* winner;           // [cells], filled with -1
   long* cand_cell;       // [5*na*nt], -1 = invalid
   float* cand;           // [5*na*nt][5]: iou, d(1-eiou)/d(raw0..3)
-  float* acc;            // [8]: sum(1-eiou), count, sum BCE obj, number of rejected target rows, sum BCE cls, 3 unused   (zeroed)
+  float* acc;            // [LY_LOSS_ACC], zeroed, 8-byte aligned: see LY_LOSS_ACC
   float* tbox;           // optional [5*na*nt][4]: (gx - gi, gy - gj, gw, gh) of every valid candidate (build_targets' tbox)
   float cp, cn, cls_pw, obj_pw;      // class targets (label smoothing: 1 - eps/2, eps/2), positive weights of the two BCEs
 };
@@ -107,7 +129,7 @@ __global__ __launch_bounds__(LY_THREADS) void ly_loss_match_kernel(const LyLossL
   const float cf = tg[1];
   const bool cls_ok = L.no - 5 <= 1 || (cf > -1.f && cf < (float)(L.no - 5));
   const bool sane = tg[0] >= 0.f && b < L.bs && gx == gx && gy == gy && gw == gw && gh == gh && cls_ok;
-  if (!sane && !padding && k == 0 && a == 0) atomicAdd(L.acc + 3, 1.f);
+  if (!sane && !padding && k == 0 && a == 0) atomicAdd(L.acc + LY_LOSS_BAD, 1.f);
   bool ok = sane && fmaxf(fmaxf(rw, 1.f / rw), fmaxf(rh, 1.f / rh)) < L.anchor_t;
   const float g = 0.5f;
   float ox = 0.f, oy = 0.f;
@@ -134,15 +156,15 @@ __global__ __launch_bounds__(LY_THREADS) void ly_loss_match_kernel(const LyLossL
     c[2] = -e.d[1] * 2.f * s1 * (1.f - s1);
     c[3] = -e.d[2] * 8.f * s2 * s2 * (1.f - s2) * aw;
     c[4] = -e.d[3] * 8.f * s3 * s3 * (1.f - s3) * ah;
-    atomicAdd(L.acc + 0, 1.f - e.v);
-    atomicAdd(L.acc + 1, 1.f);
+    ly_loss_add(L.acc, LY_LOSS_BOX, 1.f - e.v);
+    atomicAdd(L.acc + LY_LOSS_COUNT, 1.f);
     atomicMax(L.winner + cell, (int)idx);
     const int nc = L.no - 5;
     if (nc > 1) {                                                          // class BCE of this matched row (utils/loss.py:168-173)
       const int cls = (int)tg[1];
       float sc = 0.f;
       for (int q = 0; q < nc; ++q) sc += ly_bce(pr[5 + q], q == cls ? L.cp : L.cn, L.cls_pw);
-      atomicAdd(L.acc + 4, sc);
+      ly_loss_add(L.acc, LY_LOSS_CLS, sc);
     }
   }
   L.cand_cell[idx] = cell;
@@ -155,7 +177,7 @@ __global__ __launch_bounds__(LY_THREADS) void ly_loss_apply_kernel(const LyLossL
   const long cell = L.cand_cell[idx];
   if (cell < 0) return;
   const float* c = L.cand + idx * 5;
-  const float scale = box_gain * (float)L.bs / L.acc[1];                   // d/d(1-eiou) of  box * mean(1-eiou) * bs
+  const float scale = box_gain * (float)L.bs / L.acc[LY_LOSS_COUNT];                   // d/d(1-eiou) of  box * mean(1-eiou) * bs
   float* d = L.dp + cell * L.no;
 #pragma unroll
   for (int r = 0; r < 4; ++r) atomicAdd(d + r, scale * c[1 + r]);
@@ -164,7 +186,7 @@ __global__ __launch_bounds__(LY_THREADS) void ly_loss_apply_kernel(const LyLossL
   if (nc > 1) {                                                            // d/dx of  cls * mean over (rows, classes) of BCE * bs
     const long t = idx % L.nt;
     const int cls = (int)L.targets[t * 6 + 1];
-    const float cs = cls_gain * (float)L.bs / (L.acc[1] * (float)nc);
+    const float cs = cls_gain * (float)L.bs / (L.acc[LY_LOSS_COUNT] * (float)nc);
     const float* pr = L.p + cell * L.no;
     for (int q = 0; q < nc; ++q) atomicAdd(d + 5 + q, cs * ly_bce_grad(pr[5 + q], q == cls ? L.cp : L.cn, L.cls_pw));
   }
@@ -183,12 +205,13 @@ __global__ __launch_bounds__(LY_THREADS) void ly_loss_obj_kernel(const LyLossLev
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(L.acc + 2, red[0] + red[1] + red[2] + red[3]);
+  if (threadIdx.x == 0) ly_loss_add(L.acc, LY_LOSS_OBJ, red[0] + red[1] + red[2] + red[3]);
 }
 
 extern "C" int ly_loss_level(const float* p, float* dp, const float* anchors, const float* targets, int bs, int na, int ny, int nx, int no, long nt,
                              float anchor_t, float box_gain, float obj_gain, float balance, float* tobj, int* winner, long* cand_cell, float* cand,
                              float* acc, float* tbox, int match_only, float cls_gain, float cp, float cn, float cls_pw, float obj_pw, void* stream) {
+  LY_CHECK(((uintptr_t)acc & 7) == 0, "loss_level: acc must be 8-byte aligned (64-bit integer atomics)");
   LY_CHECK(p && (dp || match_only) && anchors && tobj && winner && acc && (nt == 0 || (targets && cand_cell && cand)), "loss_level: null pointer");
   LY_CHECK(bs > 0 && na > 0 && ny > 0 && nx > 0 && no >= 5 && nt >= 0, "loss_level: bad sizes");
   const long cells = (long)bs * na * ny * nx;
@@ -212,19 +235,20 @@ extern "C" int ly_loss_level(const float* p, float* dp, const float* anchors, co
   return 0;
 }
 
-// out[0] = total loss, out[1..3] = (lbox, lobj, lcls) as the reference returns them; acc = [nl][8] level accumulators
+// out[0] = total loss, out[1..3] = (lbox, lobj, lcls) as the reference returns them; acc = [nl][LY_LOSS_ACC] level accumulators
 __global__ void ly_loss_finish_kernel(const float* __restrict__ acc, int nl, const float* __restrict__ cells, const float* __restrict__ balance,
                                       float box_gain, float obj_gain, float cls_gain, int nc, float bs, float* __restrict__ out) {
   if (threadIdx.x != 0) return;
   float lbox = 0.f, lobj = 0.f, lcls = 0.f, bad = 0.f;
   for (int i = 0; i < nl; ++i) {
-    const float* a = acc + 8 * i;
-    bad += a[3];
-    if (a[1] > 0.f) {
-      lbox += a[0] / a[1];
-      if (nc > 1) lcls += a[4] / (a[1] * (float)nc);
+    const float* a = acc + LY_LOSS_ACC * i;
+    const float count = a[LY_LOSS_COUNT];
+    bad += a[LY_LOSS_BAD];
+    if (count > 0.f) {
+      lbox += ly_loss_sum(a, LY_LOSS_BOX) / count;
+      if (nc > 1) lcls += ly_loss_sum(a, LY_LOSS_CLS) / (count * (float)nc);
     }
-    lobj += a[2] / cells[i] * balance[i];
+    lobj += ly_loss_sum(a, LY_LOSS_OBJ) / cells[i] * balance[i];
   }
   lbox *= box_gain;
   lobj *= obj_gain;

@@ -20,17 +20,24 @@
 //                   atomics only, the result does not depend on arrival order.
 //   ly_val_advance  one thread: cursor += bs, behind ly_val_match on the same stream — a captured (match, advance) pair replays batch
 //                   after batch.
+//   ly_val_confusion  ConfusionMatrix.process_batch (utils/metrics.py; val.py calls it per image with labels, at conf 0.25 / IoU 0.45) for the same
+//                   inputs, one block per image, ADDED to a [(nc + 1)^2] int32 matrix (row: predicted class, column: true class, nc:
+//                   background).  Labels and detections are prepared as above.  The reference keeps the pairs with IoU > iou_thres, sorts
+//                   them by IoU, keeps the first pair of every detection, sorts again, keeps the first pair of every label.  In closed form,
+//                   over the detections with conf > conf_thres: l*(d) = the label OF ANY CLASS with the largest IoU > iou_thres (lowest
+//                   row on equal IoU); d*(l) = the detection with the largest IoU among those with l* = l (lowest index on equal IoU).  A
+//                   label with a d* counts in M[cls(d*), cls(l)], one without in M[nc, cls(l)]; a kept detection that is not the d* of
+//                   its l* counts in M[cls(d), nc] — but only when the image has at least one match (the reference's `if n:`); an image
+//                   without labels adds nothing (val.py calls process_batch only for images with labels).
+//                   d* comes from a 64-bit LDS atomicMax of (IoU bits << 32) | ~d per label: integer atomics only, independent of
+//                   arrival order.  The counts are pre-summed in LDS when the matrix is small (for nc = 1 every add hits one of four cells).
 // The file is compiled with -ffp-contract=off: every product, sum and quotient above is the float32 operation the reference performs, in its
 // order, so IoUs are bit-equal to the reference's and the `>= level` decisions are the same.
 #include <limits.h>
 
-#include "ly_boxes.hpp"                 // ly_val_native: scale_boxes with ratio_pad + clip_boxes
-#include "ly_common.hpp"
-#include "ly_params.h"
+#include "ly_val_labels.hpp"            // label staging, box_iou, the overflow bits; ly_boxes.hpp: ly_val_native
 
 #define LY_VAL_LEVELS 10                 // val.py:171 `iouv = torch.linspace(0.5, 0.95, 10)`; one uint16 bit per level
-#define LY_VAL_OVF_LABELS 1              // bits of the per-slot overflow flag
-#define LY_VAL_OVF_CLASS 2
 
 static_assert(LY_VAL_MAX_LABELS >= 512 && LY_VAL_MAX_LABELS * (LY_VAL_LEVELS + 6) * 4 + 64 <= 65536, "labels + first[][] must fit static LDS");
 
@@ -47,51 +54,17 @@ __global__ __launch_bounds__(LY_THREADS) void ly_val_match_kernel(const float* _
   __shared__ int s_first[LY_VAL_MAX_LABELS * LY_VAL_LEVELS];
   __shared__ int s_wcnt[LY_THREADS / LY_WAVE];
   __shared__ int s_ovf;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (LY_WAVE - 1), wave = tid / LY_WAVE;
+  const int b = blockIdx.x, tid = threadIdx.x;
   const long slot = (long)cursor[0] + b;
   if (slot < 0 || slot >= capacity) return;                 // past the accumulator: nothing is written (the host compares cursor and capacity)
-  const bool native = shapes != nullptr;
-  float h0 = 0.f, w0 = 0.f, gain = 1.f, padw = 0.f, padh = 0.f;
-  if (native) { const float* s = shapes + (long)b * 5; h0 = s[0]; w0 = s[1]; gain = s[2]; padw = s[3]; padh = s[4]; }
+  const LyValGeom g = ly_val_geom(shapes, b);
   int* hist = nt_class + slot * nc;
   for (int c = tid; c < nc; c += LY_THREADS) hist[c] = 0;
   if (tid == 0) s_ovf = 0;
   __syncthreads();
 
-  // ---- labels of image b, in row order
-  int nl = 0;                                                // labels seen so far (block-uniform)
-  for (long base = 0; base < nt; base += LY_THREADS) {
-    const long r = base + tid;
-    const bool mine = r < nt && targets[r * 6] == (float)b;
-    const unsigned long long bal = __ballot(mine);
-    if (lane == 0) s_wcnt[wave] = __popcll(bal);
-    __syncthreads();
-    int pos = nl + __popcll(bal & ((1ull << lane) - 1ull)), total = 0;
-    for (int k = 0; k < LY_THREADS / LY_WAVE; ++k) {
-      if (k < wave) pos += s_wcnt[k];
-      total += s_wcnt[k];
-    }
-    if (mine) {
-      const float* t = targets + r * 6;
-      const float c = t[1];
-      const int ci = (int)c;
-      if (c >= 0.f && c < (float)nc && (float)ci == c) atomicAdd(hist + ci, 1);
-      else atomicOr(&s_ovf, LY_VAL_OVF_CLASS);
-      if (pos < LY_VAL_MAX_LABELS) {
-        const float x = t[2] * W, y = t[3] * H, w = t[4] * W, h = t[5] * H;          // val.py:217
-        float x1 = x - w / 2, y1 = y - h / 2, x2 = x + w / 2, y2 = y + h / 2;        // xywh2xyxy (utils/general.py:760-767)
-        if (native) {
-          x1 = ly_val_native(x1, padw, gain, w0); x2 = ly_val_native(x2, padw, gain, w0);
-          y1 = ly_val_native(y1, padh, gain, h0); y2 = ly_val_native(y2, padh, gain, h0);
-        }
-        s_box[pos][0] = x1; s_box[pos][1] = y1; s_box[pos][2] = x2; s_box[pos][3] = y2;
-        s_cls[pos] = c;
-        s_row[pos] = (int)r;
-      }
-    }
-    nl += total;
-    __syncthreads();                                         // s_wcnt is rewritten by the next chunk
-  }
+  // ---- labels of image b, in row order (ly_val_labels.hpp)
+  int nl = ly_val_stage_labels(targets, nt, b, W, H, g, nc, hist, &s_ovf, s_box, s_cls, s_row, s_wcnt);
   const bool too_many = nl > LY_VAL_MAX_LABELS;
   if (too_many) nl = 0;                                      // the image is flagged and its matching skipped
   for (int i = tid; i < nl * LY_VAL_LEVELS; i += LY_THREADS) s_first[i] = INT_MAX;
@@ -113,19 +86,14 @@ __global__ __launch_bounds__(LY_THREADS) void ly_val_match_kernel(const float* _
       float x1 = p[0], y1 = p[1], x2 = p[2], y2 = p[3];
       cf = p[4];
       cl = single_cls ? 0.f : p[5];
-      if (native) {
-        x1 = ly_val_native(x1, padw, gain, w0); x2 = ly_val_native(x2, padw, gain, w0);
-        y1 = ly_val_native(y1, padh, gain, h0); y2 = ly_val_native(y2, padh, gain, h0);
+      if (g.native) {
+        x1 = ly_val_native(x1, g.padw, g.gain, g.w0); x2 = ly_val_native(x2, g.padw, g.gain, g.w0);
+        y1 = ly_val_native(y1, g.padh, g.gain, g.h0); y2 = ly_val_native(y2, g.padh, g.gain, g.h0);
       }
       const float area_d = (x2 - x1) * (y2 - y1);
       for (int l = 0; l < nl; ++l) {
         if (s_cls[l] != cl) continue;
-        const float a1x = s_box[l][0], a1y = s_box[l][1], a2x = s_box[l][2], a2y = s_box[l][3];
-        float iw = fminf(a2x, x2) - fmaxf(a1x, x1), ih = fminf(a2y, y2) - fmaxf(a1y, y1);
-        iw = iw < 0.f ? 0.f : iw;
-        ih = ih < 0.f ? 0.f : ih;
-        const float inter = iw * ih;
-        const float iou = inter / ((((a2x - a1x) * (a2y - a1y) + area_d) - inter) + 1e-7f);
+        const float iou = ly_val_iou(s_box[l], x1, y1, x2, y2, area_d);
         if (iou > best) { best = iou; best_l = l; }           // strict: the lowest label row keeps an equal IoU
       }
       if (best_l >= 0) {
@@ -162,6 +130,98 @@ __global__ __launch_bounds__(LY_THREADS) void ly_val_match_kernel(const float* _
   }
 }
 
+#define LY_VAL_CM_LDS 1024                // matrices of up to this many cells are pre-summed in LDS (nc <= 31)
+#define LY_VAL_CM_MAX_DET 16384           // l*(d) of every detection is kept in dynamic LDS, 2 bytes each
+
+__global__ __launch_bounds__(LY_THREADS) void ly_val_confusion_kernel(const float* __restrict__ dets, const int* __restrict__ counts, int max_det,
+                                                                      const float* __restrict__ targets, long nt, float W, float H,
+                                                                      const float* __restrict__ shapes, float conf_thres, float iou_thres,
+                                                                      int single_cls, int nc, int* matrix, int* flags) {
+  __shared__ float s_box[LY_VAL_MAX_LABELS][4];
+  __shared__ float s_cls[LY_VAL_MAX_LABELS];
+  __shared__ unsigned long long s_best[LY_VAL_MAX_LABELS];  // (IoU bits << 32) | ~d of the label's best detection; 0: none
+  __shared__ int s_m[LY_VAL_CM_LDS];
+  __shared__ int s_wcnt[LY_THREADS / LY_WAVE];
+  __shared__ int s_ovf, s_any;
+  extern __shared__ short s_lstar[];                         // [max_det]: l*(d); -1: d is not counted (dropped), -2: kept without a label
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const LyValGeom g = ly_val_geom(shapes, b);
+  const int side = nc + 1, cells = side * side;
+  const bool presum = cells <= LY_VAL_CM_LDS;
+  if (tid == 0) { s_ovf = 0; s_any = 0; }
+  if (presum)
+    for (int i = tid; i < cells; i += LY_THREADS) s_m[i] = 0;
+  __syncthreads();
+  int nl = ly_val_stage_labels(targets, nt, b, W, H, g, nc, nullptr, &s_ovf, s_box, s_cls, nullptr, s_wcnt);
+  const bool too_many = nl > LY_VAL_MAX_LABELS;
+  if (too_many) nl = 0;                                      // the image is flagged and skipped
+  for (int l = tid; l < nl; l += LY_THREADS) s_best[l] = 0ull;
+  __syncthreads();
+  if (nl > 0) {                                              // block-uniform; an image without labels adds nothing
+    int n = counts[b];
+    n = n < 0 ? 0 : (n > max_det ? max_det : n);
+    // ---- kept detections: the best label of any class above iou_thres; the label keeps its best detection
+    for (int d = tid; d < n; d += LY_THREADS) {
+      const float* p = dets + ((long)b * max_det + d) * 6;
+      int ls = -1;
+      if (p[4] > conf_thres) {
+        if (!single_cls && !ly_val_class_ok(p[5], nc)) {
+          atomicOr(&s_ovf, LY_VAL_OVF_CLASS);                // a detection class outside [0, nc): flagged, not counted
+        } else {
+          float x1 = p[0], y1 = p[1], x2 = p[2], y2 = p[3];
+          if (g.native) {
+            x1 = ly_val_native(x1, g.padw, g.gain, g.w0); x2 = ly_val_native(x2, g.padw, g.gain, g.w0);
+            y1 = ly_val_native(y1, g.padh, g.gain, g.h0); y2 = ly_val_native(y2, g.padh, g.gain, g.h0);
+          }
+          const float area_d = (x2 - x1) * (y2 - y1);
+          float best = iou_thres;
+          ls = -2;
+          for (int l = 0; l < nl; ++l) {
+            if (!ly_val_class_ok(s_cls[l], nc)) continue;    // flagged by the staging, not counted
+            const float iou = ly_val_iou(s_box[l], x1, y1, x2, y2, area_d);
+            if (iou > best) { best = iou; ls = l; }          // strict: above the threshold, and the lowest label row keeps an equal IoU
+          }
+          if (ls >= 0) {
+            atomicMax(&s_best[ls], ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)~d);       // best > 0: its bits order as integers
+            s_any = 1;                                       // every writer stores the same value
+          }
+        }
+      }
+      s_lstar[d] = (short)ls;
+    }
+    __syncthreads();
+    // ---- labels: matched -> M[cls(d*), cls(l)], else the background row
+    for (int l = tid; l < nl; l += LY_THREADS) {
+      if (!ly_val_class_ok(s_cls[l], nc)) continue;
+      const int gc = (int)s_cls[l];
+      int pc = nc;
+      if (s_best[l]) {
+        const int d = (int)~(unsigned)s_best[l];
+        pc = single_cls ? 0 : (int)dets[((long)b * max_det + d) * 6 + 5];
+      }
+      atomicAdd(presum ? &s_m[pc * side + gc] : &matrix[pc * side + gc], 1);
+    }
+    // ---- kept detections that did not get their label -> the background column, only in an image with a match (the reference's `if n:`)
+    if (s_any) {
+      for (int d = tid; d < n; d += LY_THREADS) {
+        const int ls = s_lstar[d];
+        if (ls == -1 || (ls >= 0 && (int)~(unsigned)s_best[ls] == d)) continue;
+        const int pc = single_cls ? 0 : (int)dets[((long)b * max_det + d) * 6 + 5];
+        atomicAdd(presum ? &s_m[pc * side + nc] : &matrix[pc * side + nc], 1);
+      }
+    }
+    if (presum) {
+      __syncthreads();
+      for (int i = tid; i < cells; i += LY_THREADS)
+        if (s_m[i]) atomicAdd(&matrix[i], s_m[i]);
+    }
+  }
+  if (tid == 0) {
+    const int f = s_ovf | (too_many ? LY_VAL_OVF_LABELS : 0);
+    if (f) atomicOr(flags, f);
+  }
+}
+
 __global__ void ly_val_advance_kernel(int* cursor, int bs) { cursor[0] += bs; }
 
 extern "C" int ly_val_match(const float* dets, const int* counts, int bs, int max_det, const float* targets, long nt, int W, int H,
@@ -185,6 +245,22 @@ extern "C" int ly_val_match(const float* dets, const int* counts, int bs, int ma
 extern "C" int ly_val_advance(int* cursor, int bs, void* stream) {
   LY_CHECK(cursor && bs > 0, "val_advance: bad arguments (bs=%d)", bs);
   hipLaunchKernelGGL(ly_val_advance_kernel, dim3(1), dim3(1), 0, reinterpret_cast<hipStream_t>(stream), cursor, bs);
+  LY_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ly_val_confusion(const float* dets, const int* counts, int bs, int max_det, const float* targets, long nt, int W, int H,
+                                const float* shapes, float conf_thres, float iou_thres, int single_cls, int nc, int* matrix, int* flags,
+                                void* stream) {
+  LY_CHECK(dets && counts && matrix && flags, "val_confusion: null pointer");
+  LY_CHECK(bs > 0 && max_det > 0 && max_det <= LY_VAL_CM_MAX_DET && W > 0 && H > 0, "val_confusion: bad sizes (bs=%d max_det=%d [1, %d] W=%d H=%d)", bs,
+           max_det, LY_VAL_CM_MAX_DET, W, H);
+  LY_CHECK(nt >= 0 && nt <= INT_MAX && (targets || nt == 0), "val_confusion: bad targets (nt=%ld)", nt);
+  LY_CHECK(nc >= 1 && nc <= 4096, "val_confusion: nc=%d outside [1, 4096]", nc);
+  LY_CHECK(iou_thres >= 0.f, "val_confusion: iou_thres=%f is negative", (double)iou_thres);
+  hipLaunchKernelGGL(ly_val_confusion_kernel, dim3((unsigned)bs), dim3(LY_THREADS), (size_t)max_det * sizeof(short),
+                     reinterpret_cast<hipStream_t>(stream), dets, counts, max_det, targets, nt, (float)W, (float)H, shapes, conf_thres, iou_thres,
+                     single_cls, nc, matrix, flags);
   LY_LAUNCH_CHECK();
   return 0;
 }

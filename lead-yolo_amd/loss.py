@@ -17,6 +17,7 @@ import torch
 
 from . import capi, ops
 
+ACC = 16            # floats per level accumulator (LY_LOSS_ACC in csrc/ly_loss.hip; [:, 7]: rejected target rows)
 DEFAULT_HYP = dict(box=0.05, cls=0.5, cls_pw=1.0, obj=1.0, obj_pw=1.0, anchor_t=4.0, fl_gamma=0.0, label_smoothing=0.0)
 
 
@@ -62,12 +63,13 @@ class ComputeLoss:
         cells = [int(p.shape[0] * p.shape[1] * p.shape[2] * p.shape[3]) for p in preds]
         k = self._consts(dev, cells)
         ncand = max(5 * na * nt, 1)
-        zero = ops.zeros_f32(sum(cells) + 8 * nl, dev)                                       # tobj of every level + accumulators (step pool)
+        at = (sum(cells) + 1) // 2 * 2                                                       # the accumulators hold int64 sums: 8-byte aligned
+        zero = ops.zeros_f32(at + ACC * nl, dev)                                             # tobj of every level + accumulators (step pool)
         winner = torch.full((sum(cells),), -1, dtype=torch.int32, device=dev)
         cand_cell = torch.empty((nl, ncand), dtype=torch.int64, device=dev)
         cand = torch.empty((nl, ncand, 5), dtype=torch.float32, device=dev)
         tbox = torch.empty((nl, ncand, 4), dtype=torch.float32, device=dev) if match_only else None
-        acc = zero[sum(cells):].view(nl, 8)
+        acc = zero[at:].view(nl, ACC)
         dps, off = [], 0
         st = capi.stream_ptr()
         for i, p in enumerate(preds):
@@ -90,7 +92,7 @@ class ComputeLoss:
         targets = self._check(p, targets)
         preds = [t.detach().float().contiguous() for t in p]
         r = self._levels(preds, targets, match_only=True)
-        if float(r["acc"][:, 3].sum()) > 0:
+        if float(r["acc"][:, 7].sum()) > 0:
             raise IndexError("build_targets: a target row has an image index outside the batch, a class outside [0, nc) (nc > 1), or a NaN")
         tcls, tbox, indices, anch = [], [], [], []
         nt = r["nt"]

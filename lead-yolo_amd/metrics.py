@@ -3,6 +3,8 @@
   match_padded   csrc/ly_metrics.hip `ly_val_match`: labels of every image prepared as val.py:217 / :157-162 do, `process_batch`
                  (val.py:79-101) for the whole batch in one launch on what `nms_padded` returns; no host synchronisation
   Validator      update() per batch (nms_padded -> ly_val_match -> ly_val_advance: sync-free, capturable), compute() once per validation
+  ConfusionMatrix  utils/metrics.py `class ConfusionMatrix`: `ly_val_confusion`, its process_batch for a whole batch in one launch, added to
+                 a device matrix; Validator(confusion=True) feeds one with what it scores
   ap_per_class   utils/metrics.py:31-95, compute_ap utils/metrics.py:98-123, as float64 numpy
 
 ap_per_class / compute_ap stay on the host on purpose: they run once per validation, after ONE device-to-host copy of the accumulator
@@ -10,7 +12,7 @@ ap_per_class / compute_ap stay on the host on purpose: they run once per validat
 and a few cumulative sums over those rows; the reference does the same in numpy.  What costs time in the reference is the per-image loop in
 front of them, and that is the part the kernel replaces.
 
-Out of scope: the confusion matrix, plots, the COCO json and `save_hybrid` labels of val.py."""
+Out of scope: plots (the confusion matrix is returned as numbers), the COCO json and `save_hybrid` labels of val.py."""
 import collections
 
 import numpy as np
@@ -143,22 +145,28 @@ def _levels(device):
     return _LEVELS[key]
 
 
-def _launch(acc, dets, counts, targets, size, shapes, single_cls):
+def _inputs(who, dets, counts, targets, size, shapes):
+    """what both kernels take: -> (dets, counts, targets, shapes as contiguous float32 / int32 device tensors, bs, max_det, W, H)"""
     if not (dets.is_cuda and counts.is_cuda):
-        raise RuntimeError(f"match_padded: the HIP path needs CUDA/ROCm tensors (got {dets.device}); there is no CPU fallback")
+        raise RuntimeError(f"{who}: the HIP path needs CUDA/ROCm tensors (got {dets.device}); there is no CPU fallback")
     if dets.dim() != 3 or dets.shape[2] != 6 or counts.shape != (dets.shape[0],):
-        raise ValueError(f"match_padded: dets [bs, max_det, 6] and counts [bs] expected (got {tuple(dets.shape)}, {tuple(counts.shape)})")
+        raise ValueError(f"{who}: dets [bs, max_det, 6] and counts [bs] expected (got {tuple(dets.shape)}, {tuple(counts.shape)})")
     bs, max_det = dets.shape[0], dets.shape[1]
     W, H = (int(size), int(size)) if isinstance(size, (int, float)) else (int(size[0]), int(size[1]))
     dets = dets.float().contiguous()
     counts = counts.to(torch.int32).contiguous()
     targets = targets.to(dets.device).float().contiguous()
     if targets.dim() != 2 or targets.shape[1] != 6:
-        raise ValueError(f"match_padded: targets [nt, 6] = (image, class, x, y, w, h) expected (got {tuple(targets.shape)})")
+        raise ValueError(f"{who}: targets [nt, 6] = (image, class, x, y, w, h) expected (got {tuple(targets.shape)})")
     if shapes is not None:
         shapes = torch.as_tensor(shapes, dtype=torch.float32, device=dets.device).contiguous()
         if shapes.shape != (bs, 5):
-            raise ValueError(f"match_padded: shapes [bs, 5] = (h0, w0, gain, padw, padh) expected (got {tuple(shapes.shape)})")
+            raise ValueError(f"{who}: shapes [bs, 5] = (h0, w0, gain, padw, padh) expected (got {tuple(shapes.shape)})")
+    return dets, counts, targets, shapes, bs, max_det, W, H
+
+
+def _launch(acc, dets, counts, targets, size, shapes, single_cls):
+    dets, counts, targets, shapes, bs, max_det, W, H = _inputs("match_padded", dets, counts, targets, size, shapes)
     nt = targets.shape[0]
     lib, st = capi.lib(), capi.stream_ptr()
     capi.check(lib.ly_val_match(_p(dets), _p(counts), bs, max_det, _p(targets) if nt else _p(None), nt, W, H, _p(shapes), _p(_levels(dets.device)),
@@ -181,6 +189,53 @@ def match_padded(dets, counts, targets, size, shapes=None, single_cls=False, out
     return out
 
 
+class ConfusionMatrix:
+    """utils/metrics.py `class ConfusionMatrix` on the device: the [nc + 1, nc + 1] matrix (row: predicted class, column: true class, index
+    nc: background) that val.py fills per image with `process_batch(predn, labelsn)` at conf 0.25 / IoU 0.45.
+
+        cm = ConfusionMatrix(nc)
+        cm.update(nms_padded(z, 0.001, 0.6)[:2], targets, size)      # ly_val_confusion: one launch per batch, no host synchronisation
+        m = cm.matrix()                                              # one synchronisation -> int64 numpy
+
+    update takes what Validator.update takes as a (dets, counts) pair and ADDS to the matrix; it is capturable into a hipGraph with static
+    inputs.  An image without labels adds nothing (val.py calls process_batch only for images with labels); one with labels and
+    no detection above `conf` sends every label to the background row.  Limits: MAX_LABELS labels per image, classes inside [0, nc):
+    matrix() raises and names the flag otherwise."""
+
+    def __init__(self, nc, conf=0.25, iou_thres=0.45, device="cuda"):
+        if not 1 <= int(nc) <= 4096:
+            raise ValueError(f"ConfusionMatrix: nc={nc} outside [1, 4096]")
+        self.nc, self.conf, self.iou_thres = int(nc), float(conf), float(iou_thres)
+        self.buf = torch.zeros((self.nc + 1) ** 2 + 1, dtype=torch.int32, device=torch.device(device))      # the matrix, then the flag word
+        self._m, self._flags = self.buf[:-1], self.buf[-1:]
+
+    def reset(self):
+        self.buf.zero_()
+        return self
+
+    def update(self, pair, targets, size, shapes=None, single_cls=False):
+        dets, counts, targets, shapes, bs, max_det, W, H = _inputs("ConfusionMatrix.update", *pair, targets, size, shapes)
+        nt = targets.shape[0]
+        capi.check(capi.lib().ly_val_confusion(_p(dets), _p(counts), bs, max_det, _p(targets) if nt else _p(None), nt, W, H, _p(shapes), self.conf,
+                                               self.iou_thres, int(bool(single_cls)), self.nc, _p(self._m), _p(self._flags), capi.stream_ptr()),
+                   "ly_val_confusion")
+
+    def matrix(self):
+        """one synchronisation, one copy -> [nc + 1, nc + 1] int64"""
+        h = self.buf.cpu().numpy()
+        if h[-1]:
+            why = " and ".join(w for bit, w in ((OVF_LABELS, f"overflow of the {MAX_LABELS} labels an image may have (that image is not counted)"),
+                                                (OVF_CLASS, f"a label or detection class outside [0, {self.nc})")) if h[-1] & bit)
+            raise RuntimeError(f"ConfusionMatrix.matrix: {why}")
+        return h[:-1].astype(np.int64).reshape(self.nc + 1, self.nc + 1)
+
+    def tp_fp(self):
+        """ConfusionMatrix.tp_fp: (true positives, false positives) per class, background left out"""
+        m = self.matrix()
+        tp = m.diagonal()
+        return tp[:-1], (m.sum(1) - tp)[:-1]
+
+
 ValResult = collections.namedtuple("ValResult", "mp mr map50 map p r ap50 ap nt classes")
 
 
@@ -195,13 +250,17 @@ class Validator:
     update(pred, targets, shapes=None): pred is Detect's inference output (or the (inference, raw maps) pair of a model in eval mode), run
     through nms_padded with val.py's settings (conf_thres 0.001, iou_thres 0.6, multi_label = nc > 1), or an (dets, counts) pair already
     produced by nms_padded.  The network input size is taken from `size` (needed with a (dets, counts) pair).
+    confusion=True: the Validator owns a ConfusionMatrix (`.confusion`, val.py's conf 0.25 / IoU 0.45) and update feeds it the same
+    detections, targets and shapes behind ly_val_match; reset() zeroes it too.
     Limits: at most `capacity_images` images between two reset() calls (update raises on the host beyond it), at most MAX_LABELS labels per
     image and label classes inside [0, nc) (compute raises and names the images otherwise), max_det detections per image."""
 
-    def __init__(self, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, capacity_images=5000, single_cls=False, size=None, device="cuda"):
+    def __init__(self, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, capacity_images=5000, single_cls=False, size=None, device="cuda",
+                 confusion=False):
         self.nc, self.conf_thres, self.iou_thres, self.max_det, self.single_cls = int(nc), conf_thres, iou_thres, int(max_det), bool(single_cls)
         self.size = size
         self.acc = MatchAccumulator(capacity_images, self.max_det, self.nc, torch.device(device))
+        self.confusion = ConfusionMatrix(self.nc, device=device) if confusion else None
         self._seen = 0                       # images handed to update() on the host (graph replays are counted by the device cursor only)
 
     @property
@@ -210,6 +269,8 @@ class Validator:
 
     def reset(self):
         self.acc.zero_()
+        if self.confusion is not None:
+            self.confusion.reset()
         self._seen = 0
         return self
 
@@ -230,6 +291,8 @@ class Validator:
             raise RuntimeError(f"Validator.update: {self._seen} + {bs} images exceed capacity_images = {self.acc.capacity}")
         _launch(self.acc, dets, counts, targets, size, shapes, self.single_cls)
         capi.check(capi.lib().ly_val_advance(_p(self.acc.cursor), bs, capi.stream_ptr()), "ly_val_advance")
+        if self.confusion is not None:
+            self.confusion.update((dets, counts), targets, size, shapes, self.single_cls)
         self._seen += bs
 
     def stats(self):
@@ -247,10 +310,10 @@ class Validator:
         keep = np.arange(self.acc.row_width)[None, :] < h.n_det[:n, None]
         return unpack_correct(h.correct[:n][keep]), h.conf[:n][keep], h.cls[:n][keep], h.nt_class[:n].sum(0)
 
-    def compute(self):
+    def compute(self, stats=None):
         """-> ValResult(mp, mr, map50, map, p, r, ap50, ap, nt, classes): val.py:183-188; the per-class arrays cover the classes that have
-        labels.  Four zeros when no detection is correct (val.py:184)."""
-        correct, conf, cls, nt = self.stats()
+        labels.  Four zeros when no detection is correct (val.py:184).  stats: what stats() returned, when the caller holds it already."""
+        correct, conf, cls, nt = stats if stats is not None else self.stats()
         classes = np.nonzero(nt > 0)[0]
         if not (len(correct) and correct.any()):
             e = np.zeros(0)

@@ -77,7 +77,7 @@ class ImageBank:
     @classmethod
     def from_native(cls, images, labels, img_size, device=None):
         """`load_image` on the device: images as decoded (uint8 HWC BGR of any sizes; numpy arrays, CPU tensors or contiguous device tensors),
-        each resized so that its long side is img_size — r = img_size / max(h0, w0), size (int(w0 * r), int(h0 * r)), truncated as
+        each resized so that its long side is img_size — predict.load_image_size, truncated as
         load_image does — by one ly_letterbox_u8 launch (layout HWC BGR) straight into the bank buffer.  The interpolation is always
         INTER_LINEAR, which is what load_image uses for the augment=True loader this bank feeds (it takes INTER_AREA only for a
         non-augmenting loader that shrinks); an image whose long side is img_size already is copied."""
@@ -92,8 +92,7 @@ class ImageBank:
         table = (capi.LyLetterboxImage * n)()
         hw, offs, off = [], [], 0
         for i, (_, h0, w0) in enumerate(src):
-            r = self.img_size / max(h0, w0)
-            nh, nw = int(h0 * r), int(w0 * r)
+            nh, nw = predict.load_image_size(h0, w0, self.img_size)
             if nh < 1 or nw < 1:
                 raise ValueError(f"ImageBank.from_native: image {i} ({h0} x {w0}) would be resized to {nh} x {nw}")
             hw.append((nh, nw))

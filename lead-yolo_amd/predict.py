@@ -96,6 +96,13 @@ def letterbox_plan(shapes_hw, new_shape=640, auto=False, scaleup=True, stride=32
     return LetterboxPlan(f, np.array(shapes, dtype=np.float32).reshape(-1, 5), np.array(val_shapes, dtype=np.float32).reshape(-1, 5))
 
 
+def load_image_size(h0, w0, img_size):
+    """utils/dataloaders.py load_image: the long side to img_size, r = img_size / max(h0, w0), both sides TRUNCATED with int() -> (h, w).  The
+    training bank (ImageBank.from_native) and the validation loader (valrun.val_plan) load their images at this size."""
+    r = int(img_size) / max(int(h0), int(w0))
+    return int(h0 * r), int(w0 * r)
+
+
 # ---- device plumbing ----------------------------------------------------------------------------------------------------------------------
 def _device(device):
     dev = torch.device(device if device is not None else "cuda")
