@@ -26,7 +26,9 @@ class GradReducer:
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         self.average = average
-        self.params = [p for p in params if p.requires_grad]
+        self._all = list(params)
+        self._mask = tuple(p.requires_grad for p in self._all)    # the buckets hold the parameters trainable NOW: reset() checks it still holds
+        self.params = [p for p in self._all if p.requires_grad]
         order = list(reversed(self.params))                       # backward order ~ reverse registration order
         # two weights whose gradients ONE kernel writes as a stacked matrix (`p._ly_grad_pair = q`, C3_CA's cv1 / cv2) sit next to each other,
         # p first — the layout optim.FusedSGD gives them on one GPU; without it the data-parallel step lost the stacked weight gradient
@@ -106,6 +108,9 @@ class GradReducer:
     # ---- per-step protocol ---------------------------------------------------------------------------
     def reset(self):
         """Call at the start of every step (instead of zero_grad(set_to_none=True))."""
+        if tuple(p.requires_grad for p in self._all) != self._mask:
+            raise RuntimeError("GradReducer: requires_grad of its parameters changed since construction (layers frozen or unfrozen): the "
+                               "buckets and hooks cover the old set — detach() and rebuild the GradReducer")
         whole = self.master_covers_all()
         if whole:
             self._master.zero_()                                  # one fill for every bucket

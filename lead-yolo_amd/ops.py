@@ -1091,8 +1091,8 @@ class GradSink:
         return t.data_ptr() in self._ptrs
 
     def target(self, p):
-        if p is None or not torch.is_tensor(p):
-            return None
+        if p is None or not torch.is_tensor(p) or not p.requires_grad:
+            return None                         # (a parameter frozen since the optimiser built its table: autograd drops what is returned for it)
         t = self.targets.get(id(p))
         if t is not None and p.grad is not t:
             return None                         # someone re-assigned .grad: fall back to autograd for this one

@@ -59,6 +59,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self._ema = None
         self._table = None
         self._grad_ptrs = None
+        self._mask = None               # requires_grad of every parameter when the table was built (_flags)
         self.grad_norm = None           # device scalar: pre-clip global gradient norm of the last step
         self._zeroed = False
         self._sink = None               # the ops.GradSink this optimiser installed; _writes_at_step: its write counter when step() last zeroed the storage
@@ -86,11 +87,15 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 src = msd[k]
                 if v.dtype != torch.float32 or src.dtype != torch.float32 or not v.is_contiguous() or not src.is_contiguous():
                     raise NotImplementedError(f"{type(self).__name__} EMA: {k} must be contiguous float32 on both sides")
-                if src.data_ptr() in pid:
+                if src.data_ptr() in pid and pid[src.data_ptr()].requires_grad:
                     ema_of[src.data_ptr()] = v
                 else:
-                    extra.append((src, v))
+                    extra.append((src, v))      # buffers, and frozen parameters: ModelEMA.update averages every floating state entry
         return ema_of, extra
+
+    def _flags(self):
+        """requires_grad of every parameter, in group order: the table, the gradient storage and the sink hold the trainable ones only"""
+        return tuple(p.requires_grad for g in self.param_groups for p in g["params"])
 
     def _grad_storage(self, p):
         """give p its persistent gradient storage -> (taps, cin) of the table entry (taps > 1: tap-major)"""
@@ -134,9 +139,15 @@ class _FusedOptimizer(torch.optim.Optimizer):
         dev = None
         entries, sizes, keep = [], [], []
         ema_of, extra = self._ema_pairs()
+        mine = self._sink.targets if self._sink is not None else {}
         for gi, group in enumerate(self.param_groups):
             for p in group["params"]:
                 if not p.requires_grad:
+                    # frozen (the reference's --freeze): no entry, so no update, no decay, no momentum.  Frozen since the last table: the
+                    # storage this optimiser gave it goes, as the reference's zero_grad() leaves None for a parameter without gradient
+                    if p.grad is not None and mine.get(id(p)) is p.grad:
+                        p.grad = None
+                    self._frozen(p)
                     continue
                 if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
                     raise NotImplementedError(f"{name} needs contiguous float32 CUDA parameters (fp32 master weights)")
@@ -153,9 +164,12 @@ class _FusedOptimizer(torch.optim.Optimizer):
             sizes.append(src.numel())
             keep += [src, v]
         if not entries:
-            raise ValueError(f"{name}: no parameters")
+            # every parameter frozen (and no EMA): a table without entries, and step() launches nothing
+            dev = next((p.device for g in self.param_groups for p in g["params"]), None)
+            if dev is None:
+                raise ValueError(f"{name}: no parameters")
         arr = (self._struct * len(entries))(*[self._struct(*e) for e in entries])
-        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone()
+        raw = torch.frombuffer(bytearray(bytes(arr) or b"\0"), dtype=torch.uint8).clone()
         blk_t, blk_o = [], []
         for i, n in enumerate(sizes):
             for off in range(0, n, CHUNK):
@@ -169,6 +183,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
         self._grad_ptrs = [(p, p.grad.data_ptr(), tuple(self.state[p][k].data_ptr() for k in self._state_keys), float(g["weight_decay"]))
                            for g in self.param_groups for p in g["params"] if p.requires_grad]
+        self._mask = self._flags()
         self._zeroed = False
         # the backward kernels may now add weight / BatchNorm gradients straight into this storage (ops.GradSink): no fresh
         # gradient tensors, no zero fills, no AccumulateGrad launches
@@ -180,6 +195,9 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
     def _begin_build(self):
         pass
+
+    def _frozen(self, p):
+        """_build met a parameter that does not require grad"""
 
     def _sync_hyper(self):
         """learning rates (and the other host-set scalars) follow param_groups — schedulers / warm-up write them; one small H2D copy per
@@ -211,7 +229,12 @@ class _FusedOptimizer(torch.optim.Optimizer):
             if capturing:
                 raise RuntimeError(f"{name}: run one eager step before capturing (the tensor table is built on the first step)")
             self._build()
-        if not capturing:
+        if self._flags() != self._mask:                    # parameters were frozen or unfrozen since the table was built
+            if capturing:
+                raise RuntimeError(f"{name}: requires_grad of its parameters changed since the last step: run one eager step before capturing "
+                                   "(the tensor table is rebuilt there)")
+            self._build()
+        elif not capturing:
             wds = {id(p): float(g["weight_decay"]) for g in self.param_groups for p in g["params"]}
             for p, ptr, sptrs, wd in self._grad_ptrs:      # gradients, state tensors and decays must still be what the table says
                 st = self.state[p]
@@ -219,8 +242,10 @@ class _FusedOptimizer(torch.optim.Optimizer):
                         or any(st.get(k) is None or st[k].data_ptr() != q for k, q in zip(self._state_keys, sptrs))):
                     self._build()
                     break
+        if not capturing:
             self._sync_hyper()
-        self._launch(self._table)
+        if self._table["n_blocks"]:
+            self._launch(self._table)
         from . import pack
         pack.touch_weights()              # parameters changed through raw pointers: packed-weight images and caches must refresh
         if self._ema is not None and not capturing:
@@ -326,6 +351,7 @@ class FusedAdam(_FusedOptimizer):
         self._T = 0                     # T before the first table is built / after load_state_dict
         self._T_dev = None              # `hyper` of the last table built: its [11] is T from then on (also after attach_ema drops the table)
         self._step0 = {}                # parameter -> value of T when its state was created (its step count is T - step0)
+        self._frozen_at = {}            # parameter with state, frozen now -> T when a table was first built without it
 
     def _steps_taken(self):
         """T (a host sync once a table has been built)"""
@@ -334,8 +360,14 @@ class FusedAdam(_FusedOptimizer):
     def _begin_build(self):
         self._T = self._steps_taken()
 
+    def _frozen(self, p):
+        if p in self._step0:
+            self._frozen_at.setdefault(p, self._T)
+
     def _param_entry(self, p, group, gi, taps, cin, e):
         st = self.state[p]
+        if p in self._frozen_at:                           # unfrozen again: the steps taken without it do not count (torch counts per parameter)
+            self._step0[p] = self._step0.get(p, self._T) + self._T - self._frozen_at.pop(p)
         if st.get("exp_avg") is None or st.get("exp_avg_sq") is None:
             st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(p), torch.zeros_like(p)
             self._step0[p] = self._T                   # no state yet: its first update is torch's step 1
@@ -384,7 +416,7 @@ class FusedAdam(_FusedOptimizer):
         for g, sg in zip(self.param_groups, sd["param_groups"]):
             for p, i in zip(g["params"], sg["params"]):
                 if i in sd["state"]:
-                    sd["state"][i]["step"] = torch.tensor(float(T - self._step0.get(p, T)), dtype=torch.float32)
+                    sd["state"][i]["step"] = torch.tensor(float(self._frozen_at.get(p, T) - self._step0.get(p, T)), dtype=torch.float32)
         return sd
 
     def load_state_dict(self, state_dict):
@@ -394,6 +426,7 @@ class FusedAdam(_FusedOptimizer):
         steps = {p: int(float(st.pop("step"))) for p, st in self.state.items() if "step" in st}
         self._T, self._T_dev = max(steps.values(), default=0), None
         self._step0 = {p: self._T - s for p, s in steps.items()}
+        self._frozen_at = {}
         for g in self.param_groups:
             g["decoupled_weight_decay"] = self.decoupled   # the update rule is this class's
             self._check_group(g)

@@ -36,6 +36,23 @@ def param_groups(model):
     return bias, decay, norm
 
 
+def freeze_layers(model, freeze):
+    """The reference's `--freeze` (the `freeze` loop of train.py, before the optimiser is made): `freeze` = N freezes layers 0 .. N-1 (a one-element list means the same), a longer
+    list freezes the layers it names.  Every parameter whose name contains `model.{i}.` for such a layer gets requires_grad = False,
+    EVERY other parameter requires_grad = True (so a second call with 0 unfreezes the model).  The model stays in .train(): the frozen
+    layers' BatchNorms keep normalising with, and updating, batch statistics.  -> the names of the frozen parameters.
+    The fused optimisers follow a changed mask at their next step; a GraphedTrainStep or a ddp.GradReducer built under another mask
+    raises and has to be rebuilt."""
+    layers = list(freeze) if isinstance(freeze, (list, tuple, range)) else [int(freeze)]
+    pre = [f"model.{i}." for i in (layers if len(layers) > 1 else range(layers[0] if layers else 0))]
+    frozen = []
+    for k, v in model.named_parameters():
+        v.requires_grad_(not any(x in k for x in pre))
+        if not v.requires_grad:
+            frozen.append(k)
+    return frozen
+
+
 def smart_optimizer(model, name="SGD", lr=0.001, momentum=0.9, decay=1e-5, fused=None, max_norm=10.0):
     """The reference's optimiser and three groups (utils/torch_utils.py:318-346): name in SGD (nesterov), Adam, AdamW (betas =
     (momentum, 0.999), AdamW's own decay 0.0), RMSProp.  fused=True (default when the parameters live on the GPU): the fused
@@ -252,6 +269,8 @@ class GraphedTrainStep:
         # (rebuilt when a gradient pointer changes).  A later eager step or a second GraphedTrainStep at another shape would otherwise
         # free memory these graphs still zero-fill and add into.
         self._pins = (ops._POOL.buf, dict(getattr(compute_loss, "_const", {})), optimizer._table)
+        # the graphs write the gradients and update the parameters of the mask they were captured under (checked at every call)
+        self._mask = optimizer._flags()
         # packed weight images were only RECORDED as refreshed during the capture: an eager forward before the first replay must rebuild them
         pack.touch_weights()
         if reducer is not None and self.accumulate == 1:
@@ -410,6 +429,9 @@ class GraphedTrainStep:
 
     def __call__(self, imgs=None, targets=None):
         from . import capi, pack
+        if self.optimizer._flags() != self._mask:          # (host flags only: nothing is launched for this)
+            raise RuntimeError("GraphedTrainStep: requires_grad of the parameters changed since the step was captured (layers frozen or "
+                               "unfrozen): the graphs still update the old set — rebuild the GraphedTrainStep")
         self._load(imgs, targets)
         _set_deferred_average(self.optimizer, self.reducer)    # an eager train_step in between may have reset the (grad_scale, defer_average) pair
         self.optimizer._sync_hyper()                       # learning-rate schedule -> device (only when it changed)
