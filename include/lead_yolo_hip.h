@@ -19,7 +19,8 @@ extern "C" {
 #endif
 
 enum { LY_F32 = 0, LY_BF16 = 1 };
-int ly_abi_version(void);      /* 5: ly_mosaic_img / ly_mosaic_labels (4: augmented inference, 3: ly_adam_step, 2: dtype-polymorphic entry points) */
+int ly_abi_version(void);      /* 5: ly_mosaic_img / ly_mosaic_labels (4: augmented inference, 3: ly_adam_step, 2: dtype-polymorphic entry points);
+                                * added since, version unchanged (new symbols only): LyMixup, ly_mosaic_mix_img, ly_mosaic_mix_labels */
 const char* ly_last_error(void);
 
 /* FasterNet MLPBlock forward, eval form (BN folded to scale/shift):
@@ -354,6 +355,25 @@ int ly_mosaic_img(const unsigned char* bank, const LyMosaicImage* imgs, int n_im
  * largest nlab of any tile; cap >= n_img * 4 * max_labels.  Replaces the label arithmetic of load_mosaic / random_perspective /
  * __getitem__ and collate_fn (utils/dataloaders.py, utils/augmentations.py).  One block.                                                   */
 int ly_mosaic_labels(const double* labels, const LyMosaicImage* imgs, int n_img, int s, int max_labels, float* targets, long cap, void* stream);
+/* The same batch with mixup (utils/dataloaders.py: `if random.random() < hyp['mixup']: img, labels = mixup(img, labels,
+ * *self.load_mosaic(...))`, utils/augmentations.py mixup).  imgs: DEVICE table of n_entry >= n_img entries: [0, n_img) are the output
+ * images as above, [n_img, n_entry) the second mosaics; mix: DEVICE table of n_img entries.  A partner entry's lut, flipud and fliplr are
+ * ignored: the HSV step and the flips come after the blend and are the primary's.                                                       */
+typedef struct LyMixup {
+  int partner;            /* table index in [n_img, n_entry) of the image's second mosaic, -1: none                       */
+  int unused;
+  double r;               /* np.random.beta(32, 32): the weight of the first image                                        */
+} LyMixup;
+/* ly_mosaic_img, except that an image with a partner is, per pixel and channel, (int)((double)c1 * r + (double)c2 * (1.0 - r)) of the two
+ * entries' warped and rounded values c1, c2 (both sampled at the same mirrored (u, v), each through its own minv) — float64, truncated,
+ * not clamped: `(im * r + im2 * (1 - r)).astype(np.uint8)` — before the primary's HSV step.  Without a partner: ly_mosaic_img's bytes.   */
+int ly_mosaic_mix_img(const unsigned char* bank, const LyMosaicImage* imgs, const LyMixup* mix, int n_img, int n_entry, int s, unsigned char* out,
+                      void* stream);
+/* ly_mosaic_labels over n_img * 8 * max_labels slots, (image, half, tile, label): half 0 is entry b, half 1 entry mix[b].partner (its own
+ * tiles, m, scale and 2s clip; the primary's flips; image index b).  Within an image the primary's rows come first
+ * (np.concatenate((labels, labels2), 0)).  cap >= n_img * 8 * max_labels.                                                               */
+int ly_mosaic_mix_labels(const double* labels, const LyMosaicImage* imgs, const LyMixup* mix, int n_img, int n_entry, int s, int max_labels,
+                         float* targets, long cap, void* stream);
 /* Adjoint of that permute for the training step (models/yolo.py:88): dp fp32 [n, na, H, W, no] -> du rows [n*H*W][ldu] of T (column a*no+o;
  * columns >= na*no written as zero: the operand of the head's dgrad / wgrad), dbias[a*no+o] += sum over pixels.  W <= 160, na*no <= ldu <= 32. */
 int ly_detect_head_bwd(const float* dp, int n_img, int H, int W, int na, int no, void* du /*T*/, int ldu, float* dbias,

@@ -10,7 +10,12 @@ batch (csrc/ly_mosaic.hip) that write the uint8 NCHW batch and the fixed-shape p
 
 The random draws happen on the host with the reference's distributions (numpy's generator, not Python's `random`: the same distributions, not the
 same stream).  Each draw is turned into one LyMosaicImage entry (placement rectangles with load_mosaic's formulas, M = T @ S @ R @ C and its
-float64 inverse, the HSV LUTs of augment_hsv, the flip bits); the table goes to the device with one non-blocking copy from pinned memory."""
+float64 inverse, the HSV LUTs of augment_hsv, the flip bits); the table goes to the device with one non-blocking copy from pinned memory.
+
+Mixup (hyp['mixup'] > 0, the reference's medium / high hyper-parameter files) is opt-in: MosaicAugment(..., allow_mixup=True).  A mosaic image
+then draws, with that probability, a second independent mosaic and a ratio from beta(32, 32); the device blends the two warped images as
+`mixup_blend` states it and appends the second mosaic's label rows, so `capacity` is batch_size * 8 * max_labels: a GraphedTrainStep fed by
+such an augmenter is constructed with targets of that shape.  copy_paste and perspective remain refused."""
 import ctypes
 import math
 
@@ -183,13 +188,24 @@ def hsv_luts(gains):
     return np.stack([((x * r[0]) % 180).astype(np.uint8), np.clip(x * r[1], 0, 255).astype(np.uint8), np.clip(x * r[2], 0, 255).astype(np.uint8)])
 
 
+def mixup_blend(a, b, r):
+    """utils/augmentations.py mixup's image: `(im * r + im2 * (1 - r)).astype(np.uint8)` — for uint8 images float64 arithmetic, then
+    truncation (r = 0.4105263202137452 takes two 114s to 113.99999999999999, stored as 113)"""
+    return (a * r + b * (1 - r)).astype(np.uint8)
+
+
 class Draw:
     """One output image's random draws.  mosaic: `sources` are the four bank indices in tile order and (xc, yc) the canvas centre; letterbox:
-    one source.  degrees / scale / shear = (x, y) / translate = (x, y) as random_perspective draws them; gains: the three HSV gains or None."""
-    __slots__ = ("mosaic", "sources", "xc", "yc", "degrees", "scale", "shear", "translate", "gains", "flipud", "fliplr")
+    one source.  degrees / scale / shear = (x, y) / translate = (x, y) as random_perspective draws them; gains: the three HSV gains or None.
+    partner: the mosaic Draw of mixup's second image (its own sources, centre and random_perspective draws; no gains and no flips: HSV and
+    the flips act on the blended image and are this draw's) or None; ratio: the weight of this image in the blend."""
+    __slots__ = ("mosaic", "sources", "xc", "yc", "degrees", "scale", "shear", "translate", "gains", "flipud", "fliplr", "partner", "ratio")
 
     def __init__(self, mosaic, sources, xc=0, yc=0, degrees=0.0, scale=1.0, shear=(0.0, 0.0), translate=(0.5, 0.5), gains=None, flipud=False,
-                 fliplr=False):
+                 fliplr=False, partner=None, ratio=None):
+        if partner is not None and not (mosaic and partner.mosaic and partner.partner is None and ratio is not None):
+            raise ValueError("Draw: a mixup partner is a mosaic draw without a partner of its own, for a mosaic draw, with a ratio")
+        self.partner, self.ratio = partner, None if ratio is None else float(ratio)
         self.mosaic, self.sources, self.xc, self.yc = bool(mosaic), [int(i) for i in sources], int(xc), int(yc)
         self.degrees, self.scale, self.shear, self.translate = float(degrees), float(scale), tuple(shear), tuple(translate)
         self.gains = None if gains is None else np.asarray(gains, dtype=np.float64)
@@ -198,23 +214,29 @@ class Draw:
 
 class Plan:
     """The parameter table of one batch: `table` (ctypes LyMosaicImage array, lut pointers unset), `luts` [n, 3, 256] uint8, the draws, and per
-    image the forward matrix M (3 x 3 float64)"""
+    image the forward matrix M (3 x 3 float64).  Mixup: `partner_table` (LyMosaicImage array, one entry per draw that has a partner, in image
+    order; None when there is none) and `mix` (LyMixup * n: partner = n + the position in partner_table, or -1; r = the draw's ratio)"""
 
-    def __init__(self, table, luts, draws, mats):
+    def __init__(self, table, luts, draws, mats, partner_table=None, mix=None):
         self.table, self.luts, self.draws, self.mats = table, luts, draws, mats
         self.n = len(draws)
+        self.partner_table = partner_table
+        self.k = len(partner_table) if partner_table is not None else 0
+        self.mix = mix if mix is not None else (capi.LyMixup * self.n)(*[capi.LyMixup(-1, 0, 0.0) for _ in range(self.n)])
 
 
 class MosaicAugment:
     """Batches of augmented training images from an ImageBank, built on the device (see the module docstring).  hyp: the reference's keys
-    (default hyp.scratch-low); mixup, copy_paste and perspective are not implemented.  capacity = batch_size * 4 * bank.max_labels target
-    rows: fixed, so the target tensor has one shape for every batch (rows past the batch's labels are padding, image index -1)."""
+    (default hyp.scratch-low); copy_paste and perspective are not implemented, mixup needs allow_mixup=True.  capacity = batch_size * 4 *
+    bank.max_labels target rows (* 8 with mixup: two mosaics per image): fixed, so the target tensor has one shape for every batch (rows past
+    the batch's labels are padding, image index -1)."""
 
-    def __init__(self, bank, hyp=None, batch_size=16, seed=0):
+    def __init__(self, bank, hyp=None, batch_size=16, seed=0, allow_mixup=False):
         h = dict(HYP_SCRATCH_LOW)
         h.update(hyp or {})
-        if h["mixup"] > 0:
-            raise NotImplementedError("MosaicAugment: mixup > 0 is not implemented on the device path")
+        if h["mixup"] > 0 and not allow_mixup:
+            raise NotImplementedError("MosaicAugment: mixup > 0 doubles the target rows (capacity = batch_size * 8 * max_labels): pass "
+                                      "allow_mixup=True and construct the training step with targets of that capacity")
         if h["copy_paste"] > 0:
             raise NotImplementedError("MosaicAugment: copy_paste > 0 is not implemented on the device path")
         if h["perspective"] != 0:
@@ -224,7 +246,8 @@ class MosaicAugment:
         self.bank, self.hyp, self.batch_size, self.seed = bank, h, int(batch_size), int(seed)
         self.img_size = bank.img_size
         self.max_labels = max(bank.max_labels, 1)
-        self.capacity = self.batch_size * 4 * self.max_labels
+        self.mixup = h["mixup"] > 0                                    # the mix entry points and the doubled capacity, for every batch
+        self.capacity = self.batch_size * (8 if self.mixup else 4) * self.max_labels
         self.rng = np.random.default_rng(self.seed)
 
     # ---- host: draws -> parameter table ------------------------------------------------------------------------------------------
@@ -249,46 +272,68 @@ class MosaicAugment:
             gains = rng.uniform(-1, 1, 3) * [h["hsv_h"], h["hsv_s"], h["hsv_v"]] + 1
         flipud = rng.random() < h["flipud"]
         fliplr = rng.random() < h["fliplr"]
-        return Draw(mosaic, sources, xc, yc, deg, sc, shear, trans, gains, flipud, fliplr)
+        partner = ratio = None
+        if self.mixup and mosaic and rng.random() < h["mixup"]:      # mixup(img, labels, *self.load_mosaic(random.choice(self.indices)))
+            src2 = [int(i) for i in rng.integers(0, n, 4)]          # random.choice(self.indices) and load_mosaic's three more
+            rng.shuffle(src2)
+            yc2, xc2 = (int(rng.uniform(s / 2, 2 * s - s / 2)) for _ in range(2))
+            deg2 = rng.uniform(-h["degrees"], h["degrees"])
+            sc2 = rng.uniform(1 - h["scale"], 1 + h["scale"])
+            shear2 = (rng.uniform(-h["shear"], h["shear"]), rng.uniform(-h["shear"], h["shear"]))
+            trans2 = (rng.uniform(0.5 - t, 0.5 + t), rng.uniform(0.5 - t, 0.5 + t))
+            partner = Draw(True, src2, xc2, yc2, deg2, sc2, shear2, trans2)
+            ratio = rng.beta(32.0, 32.0)
+        return Draw(mosaic, sources, xc, yc, deg, sc, shear, trans, gains, flipud, fliplr, partner, ratio)
 
     def plan(self, draws):
         """Plan of explicit draws (sample() draws them; tests pass their own)"""
-        s, bank = self.img_size, self.bank
         n = len(draws)
         table = (capi.LyMosaicImage * n)()
         luts = np.zeros((n, 3, 256), dtype=np.uint8)
-        mats = []
-        for b, d in enumerate(draws):
-            e = table[b]
-            for t in range(4):
-                e.tile[t].src = -1
-            if d.mosaic:
-                if len(d.sources) != 4:
-                    raise ValueError("a mosaic draw needs four sources")
-                hw = [tuple(int(v) for v in bank.hw[i]) for i in d.sources]
-                rects = mosaic_placement(s, d.xc, d.yc, hw)
-                for t, (src, (x1a, y1a, x2a, y2a, x1b, y1b, _, _)) in enumerate(zip(d.sources, rects)):
-                    self._tile(e.tile[t], src, x1a, y1a, x2a, y2a, x1b, y1b, x1a - x1b, y1a - y1b)
-                M = perspective_matrix(2 * s, 2 * s, s, s, d.degrees, d.scale, *d.shear, *d.translate)
-            else:
-                src = d.sources[0]
-                hh, ww = (int(v) for v in bank.hw[src])
-                left, top, dw, dh = letterbox_pads(s, hh, ww)
-                self._tile(e.tile[0], src, left, top, left + ww, top + hh, 0, 0, dw, dh)
-                M = perspective_matrix(s, s, s, s, d.degrees, d.scale, *d.shear, *d.translate)
-            inv = invert_affine(M)
-            e.m[:] = [float(v) for v in M[:2].reshape(-1)]
-            e.minv[:] = [float(v) for v in inv.reshape(-1).astype(np.float32)]
-            e.scale = d.scale
-            e.mosaic, e.flipud, e.fliplr = int(d.mosaic), int(d.flipud), int(d.fliplr)
-            mats.append(M)
+        mats = [self._entry(table[b], d) for b, d in enumerate(draws)]
         with_hsv = [b for b, d in enumerate(draws) if d.gains is not None]
         if with_hsv:
             r = np.stack([draws[b].gains for b in with_hsv])[:, :, None]       # hsv_luts, all images at once
             x = np.arange(0, 256, dtype=np.float64)
             luts[with_hsv] = np.stack([((x * r[:, 0]) % 180).astype(np.uint8), np.clip(x * r[:, 1], 0, 255).astype(np.uint8),
                                        np.clip(x * r[:, 2], 0, 255).astype(np.uint8)], 1)
-        return Plan(table, luts, list(draws), mats)
+        mixed = [b for b, d in enumerate(draws) if d.partner is not None]
+        if not mixed:
+            return Plan(table, luts, list(draws), mats)
+        if not self.mixup:
+            raise ValueError("MosaicAugment: a draw has a mixup partner, but this augmenter was constructed with hyp['mixup'] == 0")
+        partner_table = (capi.LyMosaicImage * len(mixed))()
+        mix = (capi.LyMixup * n)(*[capi.LyMixup(-1, 0, 0.0) for _ in range(n)])
+        for k, b in enumerate(mixed):
+            self._entry(partner_table[k], draws[b].partner)
+            mix[b] = capi.LyMixup(n + k, 0, draws[b].ratio)
+        return Plan(table, luts, list(draws), mats, partner_table, mix)
+
+    def _entry(self, e, d):
+        """fill the LyMosaicImage `e` from the draw `d` (lut unset) -> the forward matrix M"""
+        s, bank = self.img_size, self.bank
+        for t in range(4):
+            e.tile[t].src = -1
+        if d.mosaic:
+            if len(d.sources) != 4:
+                raise ValueError("a mosaic draw needs four sources")
+            hw = [tuple(int(v) for v in bank.hw[i]) for i in d.sources]
+            rects = mosaic_placement(s, d.xc, d.yc, hw)
+            for t, (src, (x1a, y1a, x2a, y2a, x1b, y1b, _, _)) in enumerate(zip(d.sources, rects)):
+                self._tile(e.tile[t], src, x1a, y1a, x2a, y2a, x1b, y1b, x1a - x1b, y1a - y1b)
+            M = perspective_matrix(2 * s, 2 * s, s, s, d.degrees, d.scale, *d.shear, *d.translate)
+        else:
+            src = d.sources[0]
+            hh, ww = (int(v) for v in bank.hw[src])
+            left, top, dw, dh = letterbox_pads(s, hh, ww)
+            self._tile(e.tile[0], src, left, top, left + ww, top + hh, 0, 0, dw, dh)
+            M = perspective_matrix(s, s, s, s, d.degrees, d.scale, *d.shear, *d.translate)
+        inv = invert_affine(M)
+        e.m[:] = [float(v) for v in M[:2].reshape(-1)]
+        e.minv[:] = [float(v) for v in inv.reshape(-1).astype(np.float32)]
+        e.scale = d.scale
+        e.mosaic, e.flipud, e.fliplr = int(d.mosaic), int(d.flipud), int(d.fliplr)
+        return M
 
     def _tile(self, tl, src, x1a, y1a, x2a, y2a, x1b, y1b, padw, padh):
         bank = self.bank
@@ -323,20 +368,28 @@ class MosaicAugment:
             if targets.dtype != torch.float32 or tuple(targets.shape) != (self.capacity, 6) or not targets.is_contiguous() or targets.device != dev:
                 raise ValueError(f"MosaicAugment: out[1] must be a contiguous float32 [{self.capacity}, 6] tensor on {dev} (got {targets.dtype} "
                                  f"{tuple(targets.shape)}): construct the step with targets of the augmenter's capacity")
-        self.launch(self.upload(plan), n, imgs, targets)
+        self.launch(self.upload(plan), n, imgs, targets, k=plan.k)
         return imgs, targets
 
     def upload(self, plan):
-        """the plan's table (+ LUTs) on the device: one non-blocking copy from a fresh pinned block on the current stream -> uint8 tensor"""
+        """the plan's table (+ with mixup the partner entries behind it and the LyMixup table; + LUTs) on the device: one non-blocking copy
+        from a fresh pinned block on the current stream -> uint8 tensor [table | partner_table | mix | luts]"""
         dev = self.bank.device
         n = plan.n
         tb = ctypes.sizeof(plan.table)
-        nbytes = tb + plan.luts.size
+        pb = ctypes.sizeof(plan.partner_table) if plan.k else 0
+        mb = ctypes.sizeof(plan.mix) if self.mixup else 0
+        nbytes = tb + pb + mb + plan.luts.size
         table_dev = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)     # a fresh pinned block: the host allocator keeps it until the copy ran
         hv = host.numpy()
         arr = (capi.LyMosaicImage * n).from_buffer(hv)
         ctypes.memmove(arr, plan.table, tb)
+        if pb:
+            ctypes.memmove(hv.ctypes.data + tb, plan.partner_table, pb)
+        if mb:
+            ctypes.memmove(hv.ctypes.data + tb + pb, plan.mix, mb)
+        tb += pb + mb
         hv[tb:] = plan.luts.reshape(-1)
         base = table_dev.data_ptr() + tb
         for b, d in enumerate(plan.draws):
@@ -345,14 +398,23 @@ class MosaicAugment:
         table_dev.copy_(host, non_blocking=True)
         return table_dev
 
-    def launch(self, table_dev, n, imgs, targets, which=3):
-        """ly_mosaic_img (which & 1) and ly_mosaic_labels (which & 2) over an uploaded table, on the current stream"""
+    def launch(self, table_dev, n, imgs, targets, which=3, k=0):
+        """ly_mosaic_img (which & 1) and ly_mosaic_labels (which & 2) over an uploaded table, on the current stream; an augmenter with mixup
+        launches ly_mosaic_mix_img / ly_mosaic_mix_labels instead, for every batch (k: the plan's partner entries, plan.k)"""
         bank, lib, st = self.bank, capi.lib(), capi.stream_ptr()
         tp = ctypes.c_void_p(table_dev.data_ptr())
+        labels = capi.ptr(bank.labels) if bank.labels.numel() else ctypes.c_void_p(0)
+        if self.mixup:
+            mp = ctypes.c_void_p(table_dev.data_ptr() + (n + k) * ctypes.sizeof(capi.LyMosaicImage))
+            if which & 1:
+                capi.check(lib.ly_mosaic_mix_img(capi.ptr(bank.data), tp, mp, n, n + k, self.img_size, capi.ptr(imgs), st), "ly_mosaic_mix_img")
+            if which & 2:
+                capi.check(lib.ly_mosaic_mix_labels(labels, tp, mp, n, n + k, self.img_size, bank.max_labels, capi.ptr(targets), self.capacity,
+                                                    st), "ly_mosaic_mix_labels")
+            return
         if which & 1:
             capi.check(lib.ly_mosaic_img(capi.ptr(bank.data), tp, n, self.img_size, capi.ptr(imgs), st), "ly_mosaic_img")
         if which & 2:
-            labels = capi.ptr(bank.labels) if bank.labels.numel() else ctypes.c_void_p(0)
             capi.check(lib.ly_mosaic_labels(labels, tp, n, self.img_size, bank.max_labels, capi.ptr(targets), self.capacity, st),
                        "ly_mosaic_labels")
 
