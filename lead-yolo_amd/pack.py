@@ -148,7 +148,7 @@ def rf3m_stream(gen_w, scale, shift, conv_w=None, mt=4, pool_stride=None):
         the value is generate.0.weight[c, t, u] * bn_scale[c, t] where the channel slot is the row's channel, else 0; slots 9, 10, 11 carry the
         BatchNorm shift split hi + lo + lolo (their B operand is 1.0);
       3 generate fragments of the chunk's tap-8 row tile (row r < 16 = channel r of the chunk), non-zero only for the unit's 4 channels;
-      [conv_w given] 2 x mt main fragments: conv.0.weight[o, c, t] with o = 32 (g mt + m) + r and (c, t) = the generated row
+      [conv_w given] 2 x mt main fragments (k-step major: fragment s2 mt + m): conv.0.weight[o, c, t] with o = 32 (g mt + m) + r and (c, t) = the generated row
         16 s2 + 8 (e//4) + 4h + e%4 of the unit's tile (the accumulator layout the generate product leaves in registers);
     then [conv_w given] mt main fragments for the tap-8 tile (one k-step: rows 8 (e//4) + 4h + e%4 = channels of the chunk).
     conv_w None: the statistics stream (generate fragments only).  With pool_stride = s (the statistics stream) rows 16 .. 31 of the tap-8
