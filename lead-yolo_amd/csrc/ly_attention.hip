@@ -618,19 +618,9 @@ extern "C" int ly_rfcbam_stats(const void* x, int ldx, int n_img, int H, int W, 
   const int IH = s * (TH - 1) + 3, IW = s * (TW - 1) + 3;
   size_t lds = sizeof(float) * ((size_t)4 * LY_ST3_WF + (size_t)IH * IW * (LY_SCC + 1) + 4 * 18 * 64);
   LY_CHECK(IH * IW * (LY_SCC / 4) <= LY_ST3_NV * LY_THREADS, "rfcbam_stats: input tile %dx%d exceeds the staging capacity", IH, IW);
-  LY_CHECK(lds <= 160 * 1024, "rfcbam_stats: tile needs %zu B LDS", lds);
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ly_rfcbam_stats3_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(ly_rfcbam_stats3_kernel<__bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
-  LY_WITH_T(dtype, hipLaunchKernelGGL(ly_rfcbam_stats3_kernel<T>, dim3(n_img * nrt * nct), dim3(LY_THREADS), lds, st, reinterpret_cast<const T*>(x), ldx, H, W, C,
-                                      Ho, Wo, s, TH, TW, nct, nrt, wg, mm, part));
-  LY_LAUNCH_CHECK();
-  return 0;
+  LY_CHECK(lds <= LY_LDS_MAX, "rfcbam_stats: tile needs %zu B LDS", lds);
+  LY_WITH_T(dtype, return ly_launch_lds<ly_rfcbam_stats3_kernel<T>>(dim3(n_img * nrt * nct), dim3(LY_THREADS), lds, st, reinterpret_cast<const T*>(x), ldx, H, W, C,
+                                                                    Ho, Wo, s, TH, TW, nct, nrt, wg, mm, part));
 }
 
 // rfa[n, y, x] = sigmoid( sum_{ch, dy, dx} w[ch][dy][dx] * mm[n, y+dy-1, x+dx-1, ch] )
@@ -871,19 +861,9 @@ extern "C" int ly_sppf_pool(const void* x, int ldx, int n_img, int H, int W, int
   LY_CHECK_DTYPE(dtype, "sppf_pool");
   LY_CHECK(x && out && k >= 1 && (k & 1) && (C & 3) == 0 && (ldx & 3) == 0 && (ldo & 3) == 0, "sppf_pool: bad arguments");
   size_t lds = sizeof(float) * 2 * (size_t)H * W * 4;
-  LY_CHECK(lds <= 160 * 1024, "sppf_pool: %dx%d map does not fit LDS (%zu B)", H, W, lds);
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ly_sppf_pool_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(ly_sppf_pool_kernel<__bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
-  LY_WITH_T(dtype, hipLaunchKernelGGL(ly_sppf_pool_kernel<T>, dim3(n_img * (C / LY_SP_CG)), dim3(LY_THREADS), lds, reinterpret_cast<hipStream_t>(stream),
-                                      reinterpret_cast<const T*>(x), ldx, H, W, C, k, reinterpret_cast<T*>(out), ldo));
-  LY_LAUNCH_CHECK();
-  return 0;
+  LY_CHECK(lds <= LY_LDS_MAX, "sppf_pool: %dx%d map does not fit LDS (%zu B)", H, W, lds);
+  LY_WITH_T(dtype, return ly_launch_lds<ly_sppf_pool_kernel<T>>(dim3(n_img * (C / LY_SP_CG)), dim3(LY_THREADS), lds, reinterpret_cast<hipStream_t>(stream),
+                                                                reinterpret_cast<const T*>(x), ldx, H, W, C, k, reinterpret_cast<T*>(out), ldo));
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1371,13 +1351,9 @@ extern "C" int ly_rfcbam_tap_moments(const void* x, int ldx, int n_img, int H, i
     constexpr int NPX = (2 * LY_TM_T + 1) * (2 * LY_TM_T + 1);
     size_t lds = (size_t)NPX * 64 * esz;
     if (lds < 4 * 27 * 64 * sizeof(float)) lds = 4 * 27 * 64 * sizeof(float);
-    LY_WITH_T(dtype, {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_rfcbam_tap_moments_s2t_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(ly_rfcbam_tap_moments_s2t_kernel<T>, dim3((unsigned)nb, (unsigned)groups), dim3(LY_THREADS), lds, reinterpret_cast<hipStream_t>(stream),
-                         reinterpret_cast<const T*>(x), ldx, n_img, H, W, C, Ho, Wo, tiles_y, tiles_x, mom);
-    });
-    LY_LAUNCH_CHECK();
-    return 0;
+    LY_WITH_T(dtype, return ly_launch_lds<ly_rfcbam_tap_moments_s2t_kernel<T>>(dim3((unsigned)nb, (unsigned)groups), dim3(LY_THREADS), lds,
+                                                                               reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const T*>(x), ldx,
+                                                                               n_img, H, W, C, Ho, Wo, tiles_y, tiles_x, mom));
   }
   long blocks = npix / 32 + 1;
   if (blocks > 1024) blocks = 1024;

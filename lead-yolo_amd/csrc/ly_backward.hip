@@ -14,6 +14,7 @@
 // :1478-1482 (MLPBlock), :1537-1561 (patch layers).
 #include "ly_tile.hpp"
 #include "ly_params.h"
+#include "ly_wgrad.hpp"
 
 // -------------------------------------------------------------------------------------------------
 // BN(train)+activation backward.  Forward:  v = a[c]*u + b[c],  y = act(v).
@@ -889,15 +890,12 @@ __device__ __forceinline__ void ly_wgrad_tiled_body(const LyWgradParams& Q, cons
 }
 
 // dw[n][tap][c] += sum over chunks of slab[chunk][tile][row][col] in a fixed order, one writer per element (the second launch of a tiled
-// weight gradient whose chunks left their tiles in LyWgradParams.ws).  Block = 64 slab columns x 16 chunk lanes.
+// weight gradient whose chunks left their tiles in LyWgradParams.ws).  Block = 64 slab columns x rls row lanes; this is the decode of a slab
+// column into (row, tap, channel), the sum is ly_wgrad_fold (ly_wgrad.hpp).
 __device__ __forceinline__ void ly_wgrad_combine_body(const LyWgradParams& P, const float* __restrict__ slab, const int chunks, const int tiles_k,
                                                       const int tiles, const int BN, const int BK, const long blk, const int rls) {
-  // rls row lanes (block = 64 columns x rls lanes, 64 rls threads) walk the chunks: 16 for the single-problem launches (hundreds of chunks
-  // per element), 4 when a group's problems have a few dozen chunks each (1024 threads with two loads apiece were all overhead: 13 us)
-  __shared__ float red[16][64];
-  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const long E = (long)tiles * BN * BK;
-  const long e = blk * 64 + cl;
+  const long e = blk * 64 + (threadIdx.x & 63);
   const int tile = (int)(e / (BN * BK));
   const int rem = (int)(e - (long)tile * (BN * BK));
   const int lr = rem / BK, lc = rem - lr * BK;
@@ -905,39 +903,7 @@ __device__ __forceinline__ void ly_wgrad_combine_body(const LyWgradParams& P, co
   const int row = tn * BN + lr, col = tk * BK + lc;
   const int tap = col / P.Cin, cch = col - tap * P.Cin;
   const bool live = e < E && row < P.n_valid && col < P.ks * P.ks * P.Cin && cch < P.c_valid;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (live) {
-    // four loads in flight per lane (the launch is a handful of dependent memory round trips: 8.6 -> ~6 us with two more in flight);
-    // the summation order is fixed, whatever the block count of the producing launch
-    const float* p = slab + e;
-    int c = rl;
-    for (; c + 7 * rls < chunks; c += 8 * rls) {        // eight loads fenced ahead of the adds (the scheduler sinks them back otherwise)
-      float v[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = p[(long)(c + rls * k) * E];
-      __builtin_amdgcn_sched_barrier(0);
-      a0 += v[0]; a1 += v[1]; a2 += v[2]; a3 += v[3];
-      a0 += v[4]; a1 += v[5]; a2 += v[6]; a3 += v[7];
-    }
-    for (; c + 3 * rls < chunks; c += 4 * rls) {
-      float v[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = p[(long)(c + rls * k) * E];
-      __builtin_amdgcn_sched_barrier(0);
-      a0 += v[0]; a1 += v[1]; a2 += v[2]; a3 += v[3];
-    }
-    if (c < chunks) a0 += p[(long)c * E];
-    if (c + rls < chunks) a1 += p[(long)(c + rls) * E];
-    if (c + 2 * rls < chunks) a2 += p[(long)(c + 2 * rls) * E];
-  }
-  red[rl][cl] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (rl == 0 && live) {
-    float sacc = 0.f;
-    for (int i = 0; i < rls; ++i) sacc += red[i][cl];
-    float* d = P.dw + (long)row * P.lddw + (long)tap * P.dw_ts + (long)cch * P.dw_cs;
-    *d += sacc;
-  }
+  ly_wgrad_fold(slab + e, E, chunks, rls, live, P.dw + (long)row * P.lddw + (long)tap * P.dw_ts + (long)cch * P.dw_cs);
 }
 __global__ __launch_bounds__(1024) void ly_wgrad_combine_kernel(const LyWgradParams P, const float* __restrict__ slab, const int chunks, const int tiles_k,
                                                                const int tiles, const int BN, const int BK, const int rls) {
@@ -945,7 +911,7 @@ __global__ __launch_bounds__(1024) void ly_wgrad_combine_kernel(const LyWgradPar
 }
 static void wgrad_combine_launch(const LyWgradParams& P, const float* slab, long chunks, int tiles_k, long tiles, int BN, int BK, hipStream_t st) {
   const long E = tiles * BN * BK;
-  const int rls = chunks <= 192 ? 4 : 16;                 // row lanes: see ly_wgrad_combine_body
+  const int rls = chunks <= 192 ? 4 : 16;                 // row lanes: see ly_wgrad_fold
   hipLaunchKernelGGL(ly_wgrad_combine_kernel, dim3((unsigned)((E + 63) / 64)), dim3(64 * rls), 0, st, P, slab, (int)chunks, tiles_k, (int)tiles, BN, BK, rls);
 }
 
@@ -1041,44 +1007,19 @@ static int launch_wgrad_tiled(const LyWgradParams& Q, bool rows, hipStream_t st)
   const dim3 grid((unsigned)tiles, (unsigned)chunks);
   const long need = chunks * tiles * (long)(BN * BK);
   float* const slab = (chunks > 1 && Q.ws && need <= Q.ws_floats) ? Q.ws : nullptr;
-  bool oct_done = false;
-  if constexpr (LyT<T>::BF) {
-   if (rows && wgrad_octets<T>(Q)) {
-    // bf16 rows with every width a multiple of 8: 16-byte staging loads (the octet form of ly_wgrad_tiled_body)
-    oct_done = true;
-    if (Q.x_scale) {
-      static bool attr = false;
-      if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_wgrad_tiled_kernel<T, BN, BK, P, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-      hipLaunchKernelGGL((ly_wgrad_tiled_kernel<T, BN, BK, P, true, true, true>), grid, dim3(LY_THREADS), lds, st, Q, tiles_k, chunk_px, slab);
-    } else {
-      static bool attr = false;
-      if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_wgrad_tiled_kernel<T, BN, BK, P, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-      hipLaunchKernelGGL((ly_wgrad_tiled_kernel<T, BN, BK, P, true, false, true>), grid, dim3(LY_THREADS), lds, st, Q, tiles_k, chunk_px, slab);
+  // <ROWS, PRO, OCT>: the x_scale prologue exists for rows only; OCT (bf16 storage, every width a multiple of 8) = 16-byte staging loads, the
+  // octet form of ly_wgrad_tiled_body
+#define WG_TILED(ROWS_, PRO_, OCT_) \
+  ly_launch_lds<ly_wgrad_tiled_kernel<T, BN, BK, P, ROWS_, PRO_, OCT_>>(grid, dim3(LY_THREADS), lds, st, Q, tiles_k, chunk_px, slab)
+  const bool pro = rows && Q.x_scale;
+  const auto launch = [&]() -> int {
+    if constexpr (LyT<T>::BF) {
+      if (wgrad_octets<T>(Q)) return !rows ? WG_TILED(false, false, true) : pro ? WG_TILED(true, true, true) : WG_TILED(true, false, true);
     }
-   }
-  }
-  if constexpr (LyT<T>::BF) {
-    if (!oct_done && !rows && wgrad_octets<T>(Q)) {
-      oct_done = true;
-      static bool attr = false;
-      if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_wgrad_tiled_kernel<T, BN, BK, P, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-      hipLaunchKernelGGL((ly_wgrad_tiled_kernel<T, BN, BK, P, false, false, true>), grid, dim3(LY_THREADS), lds, st, Q, tiles_k, chunk_px, slab);
-    }
-  }
-  if (oct_done) {
-  } else if (rows && Q.x_scale) {
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_wgrad_tiled_kernel<T, BN, BK, P, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-    hipLaunchKernelGGL((ly_wgrad_tiled_kernel<T, BN, BK, P, true, true>), grid, dim3(LY_THREADS), lds, st, Q, tiles_k, chunk_px, slab);
-  } else if (rows) {
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_wgrad_tiled_kernel<T, BN, BK, P, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-    hipLaunchKernelGGL((ly_wgrad_tiled_kernel<T, BN, BK, P, true>), grid, dim3(LY_THREADS), lds, st, Q, tiles_k, chunk_px, slab);
-  } else {
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_wgrad_tiled_kernel<T, BN, BK, P, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-    hipLaunchKernelGGL((ly_wgrad_tiled_kernel<T, BN, BK, P, false>), grid, dim3(LY_THREADS), lds, st, Q, tiles_k, chunk_px, slab);
-  }
+    return !rows ? WG_TILED(false, false, false) : pro ? WG_TILED(true, true, false) : WG_TILED(true, false, false);
+  };
+#undef WG_TILED
+  LY_TRY(launch());
   if (slab) wgrad_combine_launch(Q, slab, chunks, tiles_k, tiles, BN, BK, st);
   LY_LAUNCH_CHECK();
   return 0;
@@ -1086,8 +1027,6 @@ static int launch_wgrad_tiled(const LyWgradParams& Q, bool rows, hipStream_t st)
 
 template <typename T>
 static int wgrad_dispatch(const LyWgradParams& P, void* stream);
-bool ly_wgrad3_ok(const LyWgradParams& P);                         // ly_wgrad3.hip
-int ly_wgrad3_launch(const LyWgradParams& P, hipStream_t st);
 static int g_ly_wgrad3 = 1;
 extern "C" int ly_tune_wgrad3(int on) {                            // development switch: 0 sends 3x3 problems back to the generic tiled kernel
   const int was = g_ly_wgrad3;
@@ -1151,48 +1090,25 @@ static int wgrad_group_launch(const LyWgradParams* arr, int n, hipStream_t st) {
   for (int g = 0; g < n; ++g) any_pro = any_pro || arr[g].x_scale != nullptr;
   bool oct = true;
   for (int g = 0; g < n; ++g) oct = oct && wgrad_octets<T>(arr[g]);
-  if (gslab) {
-    bool launched = false;
+  // <PRO, GSLAB, OCT> of the rows form: the octet staging goes with the slab form (and bf16 storage) only
+#define WG_GROUP(PRO_, GSLAB_, OCT_) \
+  ly_launch_lds<ly_wgrad_tiled_group_kernel<T, BN, BK, PX, true, PRO_, GSLAB_, OCT_>>(dim3((unsigned)G.blk0[n]), dim3(LY_THREADS), lds, st, G)
+  const auto launch = [&]() -> int {
+    if (!gslab) return any_pro ? WG_GROUP(true, false, false) : WG_GROUP(false, false, false);
     if constexpr (LyT<T>::BF) {
-      if (oct && any_pro) {
-        static bool attr = false;
-        if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_wgrad_tiled_group_kernel<T, BN, BK, PX, true, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-        hipLaunchKernelGGL((ly_wgrad_tiled_group_kernel<T, BN, BK, PX, true, true, true, true>), dim3((unsigned)G.blk0[n]), dim3(LY_THREADS), lds, st, G);
-        launched = true;
-      } else if (oct) {
-        static bool attr = false;
-        if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_wgrad_tiled_group_kernel<T, BN, BK, PX, true, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-        hipLaunchKernelGGL((ly_wgrad_tiled_group_kernel<T, BN, BK, PX, true, false, true, true>), dim3((unsigned)G.blk0[n]), dim3(LY_THREADS), lds, st, G);
-        launched = true;
-      }
+      if (oct) return any_pro ? WG_GROUP(true, true, true) : WG_GROUP(false, true, true);
     }
-    if (launched) {
-    } else if (any_pro) {
-      static bool attr = false;
-      if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_wgrad_tiled_group_kernel<T, BN, BK, PX, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-      hipLaunchKernelGGL((ly_wgrad_tiled_group_kernel<T, BN, BK, PX, true, true, true>), dim3((unsigned)G.blk0[n]), dim3(LY_THREADS), lds, st, G);
-    } else {
-      static bool attr = false;
-      if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_wgrad_tiled_group_kernel<T, BN, BK, PX, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-      hipLaunchKernelGGL((ly_wgrad_tiled_group_kernel<T, BN, BK, PX, true, false, true>), dim3((unsigned)G.blk0[n]), dim3(LY_THREADS), lds, st, G);
-    }
+    return any_pro ? WG_GROUP(true, true, false) : WG_GROUP(false, true, false);
+  };
+#undef WG_GROUP
+  LY_TRY(launch());
+  if (gslab) {
     int cmax = 0;
     for (int g = 0; g < n; ++g) cmax = G.chunks[g] > cmax ? G.chunks[g] : cmax;
     const int rls = cmax <= 64 ? 4 : 16;
     hipLaunchKernelGGL(ly_wgrad_combine_group_kernel, dim3((unsigned)G.cblk0[n]), dim3(64 * rls), 0, st, G, BN, BK, rls);
     LY_LAUNCH_CHECK();
-    return 0;
   }
-  if (any_pro) {
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_wgrad_tiled_group_kernel<T, BN, BK, PX, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-    hipLaunchKernelGGL((ly_wgrad_tiled_group_kernel<T, BN, BK, PX, true, true>), dim3((unsigned)G.blk0[n]), dim3(LY_THREADS), lds, st, G);
-  } else {
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_wgrad_tiled_group_kernel<T, BN, BK, PX, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-    hipLaunchKernelGGL((ly_wgrad_tiled_group_kernel<T, BN, BK, PX, true>), dim3((unsigned)G.blk0[n]), dim3(LY_THREADS), lds, st, G);
-  }
-  LY_LAUNCH_CHECK();
   return 0;
 }
 
@@ -1328,7 +1244,7 @@ __global__ __launch_bounds__(LY_THREADS) void ly_unpatch_kernel(const T* __restr
 // -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void ly_sum_rows_kernel(const float* __restrict__ src, const long R, const long C, const long ld,
                                                           float* __restrict__ dst, const int accumulate, const int rls) {
-  __shared__ float red[16][64];                            // rls row lanes (4 for R <= 192, else 16: see ly_wgrad_combine_body)
+  __shared__ float red[16][64];                            // rls row lanes (4 for R <= 192, else 16: see ly_wgrad_fold)
   const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const long c = (long)blockIdx.x * 64 + cl;
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
@@ -2253,13 +2169,8 @@ extern "C" int ly_sppf_bwd(const void* buf, int ldb, const void* d, int ldd, int
   if (k != 5 || c % LY_SPPF_CG || (ldb & 3) || (ldd & 3) || (ldo & 3) || lds > 150 * 1024 || (long)n_img * (c / LY_SPPF_CG) > 2000000000L) return 1;
   const dim3 grid((unsigned)(n_img * (c / LY_SPPF_CG)));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  LY_WITH_T(dtype, {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_sppf_bwd_kernel<T, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((ly_sppf_bwd_kernel<T, 5>), grid, dim3(LY_THREADS), lds, st, reinterpret_cast<const T*>(buf), ldb, reinterpret_cast<const T*>(d), ldd, H, W, c,
-                       reinterpret_cast<T*>(out), ldo);
-  });
-  LY_LAUNCH_CHECK();
-  return 0;
+  LY_WITH_T(dtype, return ly_launch_lds<ly_sppf_bwd_kernel<T, 5>>(grid, dim3(LY_THREADS), lds, st, reinterpret_cast<const T*>(buf), ldb, reinterpret_cast<const T*>(d),
+                                                                  ldd, H, W, c, reinterpret_cast<T*>(out), ldo));
 }
 
 extern "C" int ly_maxpool_arg(const void* x, int ldx, int n_img, int H, int W, int C, int k, unsigned char* arg, int lda, int dtype, void* stream) {

@@ -249,7 +249,7 @@ extern "C" void ly_set_error(const char* fmt, ...);
     }                                      \
   } while (0)
 
-// hipFuncSetAttribute is per DEVICE: a launcher's "already configured" memo is a bitmask over device ordinals (one process may drive
+// A function attribute is set per DEVICE: a launcher's "already configured" memo is a bitmask over device ordinals (one process may drive
 // several GPUs: tests, nn.DataParallel-style use), not a process-wide flag
 struct LyDevOnce {
   unsigned long long mask = 0ull;
@@ -270,3 +270,35 @@ struct LyDevOnce {
       return -2;                                                  \
     }                                                             \
   } while (0)
+
+// return a launcher's error code to the caller:  LY_TRY(ly_launch_lds<k>(grid, block, lds, st, ...));
+#define LY_TRY(...)                        \
+  do {                                     \
+    const int r_ = (__VA_ARGS__);          \
+    if (r_) return r_;                     \
+  } while (0)
+
+// The LDS of one gfx950 CU: the most dynamic LDS a launch may ask for
+constexpr size_t LY_LDS_MAX = 160 * 1024;
+
+// Kernels whose dynamic LDS may exceed the 64 KB a launch gets by default.  ly_lds_allow raises KERNEL's cap to LY_LDS_MAX before its first
+// launch on the current device (the cap only permits an allocation; each launch still asks for its own `lds`) and never again: the hot path
+// and a graph capture after warm-up stay free of the call.  The memo is one LyDevOnce per kernel instantiation.  Launchers that query a
+// kernel's occupancy call ly_lds_allow themselves, ahead of the query; everything else goes through ly_launch_lds.
+template <auto KERNEL>
+int ly_lds_allow() {
+  static LyDevOnce once;
+  if (once.need()) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LY_LDS_MAX);
+    LY_CHECK(e == hipSuccess, "cannot raise a kernel's dynamic LDS cap to %zu B: %s", LY_LDS_MAX, hipGetErrorString(e));
+  }
+  return 0;
+}
+template <auto KERNEL, class... A>
+int ly_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+  LY_CHECK(lds <= LY_LDS_MAX, "launch needs %zu B of LDS (at most %zu)", lds, LY_LDS_MAX);
+  LY_TRY(ly_lds_allow<KERNEL>());
+  hipLaunchKernelGGL(KERNEL, grid, block, lds, st, args...);
+  LY_LAUNCH_CHECK();
+  return 0;
+}

@@ -535,17 +535,8 @@ static int launch_conv3(const LyConv3Params& P, hipStream_t st) {
   const int rp = conv3_row_pitch(P.TH, P.TW, ly_qrs(8 * LyT<T>::VW / 32));
   const int ps = ly_qps((P.TH + 2) * rp);
   size_t lds = LyT<T>::PL * (size_t)4 * ps;
-  void (*k)(const LyConv3Params, const int, const int, const int, const int, const int) = ly_conv3x3_kernel<T, MT, WC, LAT ? 0 : NTA>;
-  if constexpr (LAT) k = ly_conv3x3_lat_kernel<T, MT, WC>;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
-  hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(LY_THREADS), lds, st, P, gy, tiles_x, tiles_y, rp, ps);
-  LY_LAUNCH_CHECK();
-  return 0;
+  if constexpr (LAT) return ly_launch_lds<ly_conv3x3_lat_kernel<T, MT, WC>>(dim3((unsigned)nb), dim3(LY_THREADS), lds, st, P, gy, tiles_x, tiles_y, rp, ps);
+  else return ly_launch_lds<ly_conv3x3_kernel<T, MT, WC, NTA>>(dim3((unsigned)nb), dim3(LY_THREADS), lds, st, P, gy, tiles_x, tiles_y, rp, ps);
 }
 
 template <typename T>

@@ -512,13 +512,12 @@ static int launch_gemm_d2(const LyGemmParams& P, hipStream_t st) {
   long gx = (P.M + BP - 1) / BP;
   int gy = (P.N + BN - 1) / BN;
   LY_CHECK(gx < (1L << 30), "gemm: too many pixel tiles");
-  auto k = ly_gemm_kernel_d2<TI, TO, NT, MT, WC, GATHER, PRO, NCH, FAST>;
+  constexpr auto k = ly_gemm_kernel_d2<TI, TO, NT, MT, WC, GATHER, PRO, NCH, FAST>;
   static int per_cu = 0;            // co-resident blocks per CU (registers + LDS), measured once per instantiation
   if (per_cu == 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+    LY_TRY(ly_lds_allow<k>());      // ahead of the occupancy query
     int nb = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), LY_THREADS, lds);
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), LY_THREADS, lds);
     LY_CHECK(e == hipSuccess, "hipOccupancyMaxActiveBlocksPerMultiprocessor: %s", hipGetErrorString(e));
     per_cu = nb < 1 ? 1 : (nb > 8 ? 8 : nb);
   }
@@ -526,9 +525,7 @@ static int launch_gemm_d2(const LyGemmParams& P, hipStream_t st) {
   long nslots = (256L * per_cu) / gy;
   if (nslots < 1) nslots = 1;
   if (nslots > gx) nslots = gx;
-  hipLaunchKernelGGL(k, dim3((unsigned)(nslots * gy)), dim3(LY_THREADS), lds, st, P, gy, (int)nslots, (int)gx);
-  LY_LAUNCH_CHECK();
-  return 0;
+  return ly_launch_lds<k>(dim3((unsigned)(nslots * gy)), dim3(LY_THREADS), lds, st, P, gy, (int)nslots, (int)gx);
 }
 
 // Variant choice per call.  K in one or two chunks: weights resident (NCH) and, when every channel tile is full and the stores can be

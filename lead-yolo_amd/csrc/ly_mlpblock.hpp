@@ -843,18 +843,9 @@ static int launch_mlp_pconv1(const T* x, T* y, long M, int n_img, int H, int W, 
   constexpr int BP = 64 * NT;
   const long halo = T2D ? (4 * NT + 2) * 18 : BP + 2 * W + 2;
   size_t lds = LyT<T>::PL * ((size_t)BP * Gm::RS + (size_t)halo * Gm::RSP);
-  LY_CHECK(lds <= 160 * 1024, "mlpblock_pconv: tile needs %zu B of LDS (C=%d W=%d)", lds, C, W);
-  auto k = ly_mlpblock_pconv1_kernel<T, C, NT, HT, T2D>;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
+  LY_CHECK(lds <= LY_LDS_MAX, "mlpblock_pconv: tile needs %zu B of LDS (C=%d W=%d)", lds, C, W);
   long blocks = T2D ? (long)n_img * ((H + 4 * NT - 1) / (4 * NT)) * (W / 16) : (M + BP - 1) / BP;
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(LY_THREADS), lds, st, x, y, M, H, W, reinterpret_cast<const uint4*>(wp));
-  LY_LAUNCH_CHECK();
-  return 0;
+  return ly_launch_lds<ly_mlpblock_pconv1_kernel<T, C, NT, HT, T2D>>(dim3((unsigned)blocks), dim3(LY_THREADS), lds, st, x, y, M, H, W, reinterpret_cast<const uint4*>(wp));
 }
 
 // The instantiations are split over translation units (ly_mlpblock.hip: C = 16/24/40 + the C ABI, ly_mlpblock_b.hip:
@@ -875,22 +866,15 @@ static int launch_mlp_k(const T* x, T* y, long M, int n_img, int H, int W, const
   constexpr int BP = 64 * NT;
   const long halo = T2D ? (4 * NT + 2) * 18 : BP + 2 * W + 2;
   size_t lds = LyT<T>::PL * ((size_t)BP * Gm::RS + (size_t)halo * Gm::RSP) + (STATS ? 4 * 2 * Gm::HTP * 16 * sizeof(float) : 0);
-  LY_CHECK(lds <= 160 * 1024, "mlpblock: tile needs %zu B of LDS (C=%d W=%d)", lds, C, W);
-  void (*k)(const T*, T*, long, int, int, const uint4*, const uint4*, const uint4*, const float*, const float*, double*);
-  if constexpr (RING) k = ly_mlpblock_fwd_ring_kernel<T, C, NT, HT, T2D, STATS>;
-  else if constexpr (C <= 24 && T2D) k = ly_mlpblock_fwd_occ4_kernel<T, C, NT, HT, T2D, STATS>;
-  else k = ly_mlpblock_fwd_kernel<T, C, NT, HT, T2D, STATS>;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
+  LY_CHECK(lds <= LY_LDS_MAX, "mlpblock: tile needs %zu B of LDS (C=%d W=%d)", lds, C, W);
+  constexpr auto k = [] {
+    if constexpr (RING) return ly_mlpblock_fwd_ring_kernel<T, C, NT, HT, T2D, STATS>;
+    else if constexpr (C <= 24 && T2D) return ly_mlpblock_fwd_occ4_kernel<T, C, NT, HT, T2D, STATS>;
+    else return ly_mlpblock_fwd_kernel<T, C, NT, HT, T2D, STATS>;
+  }();
   long blocks = T2D ? (long)n_img * ((H + 4 * NT - 1) / (4 * NT)) * (W / 16) : (M + BP - 1) / BP;
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(LY_THREADS), lds, st, x, y, M, H, W, reinterpret_cast<const uint4*>(wp),
-                     reinterpret_cast<const uint4*>(w1), reinterpret_cast<const uint4*>(w2), s, b, stats);
-  LY_LAUNCH_CHECK();
-  return 0;
+  return ly_launch_lds<k>(dim3((unsigned)blocks), dim3(LY_THREADS), lds, st, x, y, M, H, W, reinterpret_cast<const uint4*>(wp),
+                          reinterpret_cast<const uint4*>(w1), reinterpret_cast<const uint4*>(w2), s, b, stats);
 }
 
 template <typename T, int C, int NT, int HT, int MODE>
@@ -900,25 +884,22 @@ static int launch_mlp_persist(const T* x, T* y, long M, int n_img, int H, int W,
   constexpr int PL = LyT<T>::PL, BP = 64 * NT, BPH = (4 * NT + 2) * 18;
   constexpr int NFW = Gm::PT * Gm::SP + Gm::HTP * Gm::S1 + Gm::C16 * Gm::S2;
   constexpr size_t lds = (size_t)NFW * PL * 1024 + 2 * (((size_t)PL * BP * Gm::RS + (size_t)PL * BPH * Gm::RSP + 15) / 16 * 16);
-  static_assert(lds <= 160 * 1024, "persistent MLPBlock: weights + two patch buffers must fit LDS");
+  static_assert(lds <= LY_LDS_MAX, "persistent MLPBlock: weights + two patch buffers must fit LDS");
   constexpr int PD = LY_MLP_PD;
-  auto k = ly_mlpblock_persist_kernel<T, C, NT, HT, MODE, PD>;
+  constexpr auto k = ly_mlpblock_persist_kernel<T, C, NT, HT, MODE, PD>;
   static int per_cu = 0;
   if (per_cu == 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+    LY_TRY(ly_lds_allow<k>());
     int nb = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), LY_THREADS, lds);
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), LY_THREADS, lds);
     LY_CHECK(e == hipSuccess, "hipOccupancyMaxActiveBlocksPerMultiprocessor: %s", hipGetErrorString(e));
     per_cu = nb < 1 ? 1 : (nb > 8 ? 8 : nb);
   }
   const long ntiles = (long)n_img * ((H + 4 * NT - 1) / (4 * NT)) * (W / 16);
   long blocks = 256L * per_cu;
   if (blocks > ntiles) blocks = ntiles;
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(LY_THREADS), lds, st, x, y, M, H, W, n_img, reinterpret_cast<const uint4*>(wp),
-                     reinterpret_cast<const uint4*>(w1), reinterpret_cast<const uint4*>(w2), s, b, stats);
-  LY_LAUNCH_CHECK();
-  return 0;
+  return ly_launch_lds<k>(dim3((unsigned)blocks), dim3(LY_THREADS), lds, st, x, y, M, H, W, n_img, reinterpret_cast<const uint4*>(wp),
+                          reinterpret_cast<const uint4*>(w1), reinterpret_cast<const uint4*>(w2), s, b, stats);
 }
 
 template <typename T, int C, int NT, int HT, bool T2D>

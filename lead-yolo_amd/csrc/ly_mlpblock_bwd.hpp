@@ -689,16 +689,14 @@ static int launch_mlp_bwd(LyMlpBwdArgs P, long slab_floats, int* blocks_out, hip
   const long halo = T2D ? (4 * NT + 2) * 18 : BP + 2 * P.W + 2;
   const size_t lds = (size_t)(Bg::NFP + 2 * Bg::NF1 + (PASS == 2 ? Bg::NF1T : 0)) * 1024 + (PASS == 2 ? 5 : 2) * 2 * C * 4 + 2 * (size_t)BP * Gm::RS +
                      ((size_t)halo * Gm::RSP + 15) / 16 * 16 + (PASS == 2 ? 2 * (size_t)BP * Bg::RSD : 0);
-  LY_CHECK(lds <= 160 * 1024, "mlpblock_bwd: tile needs %zu B of LDS (C=%d W=%d)", lds, C, P.W);
-  auto k = ly_mlpblock_bwd_kernel<C, HT, T2D, PASS, PD>;
-  static LyDevOnce once;
+  LY_CHECK(lds <= LY_LDS_MAX, "mlpblock_bwd: tile needs %zu B of LDS (C=%d W=%d)", lds, C, P.W);
+  constexpr auto k = ly_mlpblock_bwd_kernel<C, HT, T2D, PASS, PD>;
   static int per_cu = 0;
   static size_t lds_q = 0;
-  if (once.need() || lds_q != lds) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+  LY_TRY(ly_lds_allow<k>());        // ahead of the occupancy query
+  if (lds_q != lds) {
     int nb = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), LY_THREADS, lds);
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), LY_THREADS, lds);
     LY_CHECK(e == hipSuccess, "hipOccupancyMaxActiveBlocksPerMultiprocessor: %s", hipGetErrorString(e));
     per_cu = nb < 1 ? 1 : (nb > 8 ? 8 : nb);
     lds_q = lds;
@@ -712,8 +710,7 @@ static int launch_mlp_bwd(LyMlpBwdArgs P, long slab_floats, int* blocks_out, hip
              blocks * (long)Bg::SLAB);
   }
   P.ntiles = (int)ntiles;
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(LY_THREADS), lds, st, P);
-  LY_LAUNCH_CHECK();
+  LY_TRY(ly_launch_lds<k>(dim3((unsigned)blocks), dim3(LY_THREADS), lds, st, P));
   if (blocks_out) *blocks_out = (int)blocks;
   return 0;
 }
@@ -1118,23 +1115,21 @@ static inline bool mlp_bwd_dx_patches(int W) {
   return W >= 12 && 4 * (wp16 - W) <= wp16;
 }
 template <int C>
-static bool mlp_bwd_dx_fits(int W) { return mlp_bwd_dx_lds<C>(mlp_bwd_dx_patches(W), W) <= 160 * 1024; }
+static bool mlp_bwd_dx_fits(int W) { return mlp_bwd_dx_lds<C>(mlp_bwd_dx_patches(W), W) <= LY_LDS_MAX; }
 
 template <int C, bool T2D, bool WG>
 static int launch_mlp_bwd_dx(LyMlpDxArgs P, long slab_floats, float* dwp, int lddw, int ts, int cs, hipStream_t st) {
   using Gm = MlpGeom<C>;
   constexpr int BP = 128, PT = Gm::PT;
   const size_t lds = mlp_bwd_dx_lds<C>(T2D, P.W);
-  LY_CHECK(lds <= 160 * 1024, "mlpblock_bwd_dx: tile needs %zu B of LDS (C=%d W=%d)", lds, C, P.W);
-  auto k = ly_mlpblock_bwd_dx_kernel<C, T2D, WG>;
-  static LyDevOnce once;
+  LY_CHECK(lds <= LY_LDS_MAX, "mlpblock_bwd_dx: tile needs %zu B of LDS (C=%d W=%d)", lds, C, P.W);
+  constexpr auto k = ly_mlpblock_bwd_dx_kernel<C, T2D, WG>;
   static int per_cu = 0;
   static size_t lds_q = 0;
-  if (once.need() || lds_q != lds) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+  LY_TRY(ly_lds_allow<k>());        // ahead of the occupancy query
+  if (lds_q != lds) {
     int nb = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), LY_THREADS, lds);
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(k), LY_THREADS, lds);
     LY_CHECK(e == hipSuccess, "hipOccupancyMaxActiveBlocksPerMultiprocessor: %s", hipGetErrorString(e));
     per_cu = nb < 1 ? 1 : (nb > 4 ? 4 : nb);
     lds_q = lds;
@@ -1146,7 +1141,7 @@ static int launch_mlp_bwd_dx(LyMlpDxArgs P, long slab_floats, float* dwp, int ld
   constexpr int SL = 9 * PT * PT * 256;
   if (WG) LY_CHECK(P.slab && dwp && blocks * (long)SL <= slab_floats, "mlpblock_bwd_dx: the slab workspace holds %ld floats, %ld needed", slab_floats, blocks * (long)SL);
   P.ntiles = (int)ntiles;
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(LY_THREADS), lds, st, P);
+  LY_TRY(ly_launch_lds<k>(dim3((unsigned)blocks), dim3(LY_THREADS), lds, st, P));
   if (WG) {
     constexpr int NE = 9 * PT * PT * 64, EL = NE >= 2304 ? 32 : 8;      // 72 blocks in both cases
     hipLaunchKernelGGL((ly_mlpblock_bwd_dx_combine_kernel<C, EL>), dim3((NE + EL - 1) / EL), dim3(1024), 0, st, P.slab, (int)blocks, dwp, lddw, ts, cs);

@@ -394,23 +394,16 @@ static int launch_mlp_res(const T* x, T* y, long M, int H, int W, const void* wp
   if (BPH * Gm::G > (long)LY_RES_NVH * LY_RES_THREADS) return 1;
   const size_t lds = (size_t)((NFW * 64 + LY_RES_THREADS - 1) / LY_RES_THREADS) * LY_RES_THREADS * 16 + (size_t)BP * Gm::RS + ((size_t)BPH * Gm::RSP + 15) / 16 * 16 +
                      (stats ? (size_t)LY_RES_WAVES : (size_t)1) * 2 * Gm::HTP * 16 * sizeof(float);
-  if (lds > 160 * 1024) return 1;
+  if (lds > LY_LDS_MAX) return 1;
   // one block per CU; every block the same number of pixels (a multiple of 16), as few runs as that allows
   long blocks = (M + BP - 1) / BP;
   if (blocks > 256) blocks = 256;
   long per_block = ((M + blocks - 1) / blocks + 15) / 16 * 16;
   blocks = (M + per_block - 1) / per_block;
-  void (*k)(const T*, T*, long, int, int, int, const uint4*, const uint4*, const uint4*, const float*, const float*, double*);
-  if (stats) k = ly_mlpblock_res_kernel<T, C, NT, HT, true, D>;
-  else k = ly_mlpblock_res_kernel<T, C, NT, HT, false, D>;
-  static bool configured[2] = {false, false};
-  if (!configured[stats ? 1 : 0]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured[stats ? 1 : 0] = true;
-  }
-  hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(LY_RES_THREADS), lds, st, x, y, M, H, W, (int)per_block, reinterpret_cast<const uint4*>(wp),
-                     reinterpret_cast<const uint4*>(w1), reinterpret_cast<const uint4*>(w2), s, b, stats);
-  LY_LAUNCH_CHECK();
-  return 0;
+#define LY_RES_LAUNCH(STATS_)                                                                                                                  \
+  ly_launch_lds<ly_mlpblock_res_kernel<T, C, NT, HT, STATS_, D>>(dim3((unsigned)blocks), dim3(LY_RES_THREADS), lds, st, x, y, M, H, W, (int)per_block, \
+                                                                 reinterpret_cast<const uint4*>(wp), reinterpret_cast<const uint4*>(w1),       \
+                                                                 reinterpret_cast<const uint4*>(w2), s, b, stats)
+  return stats ? LY_RES_LAUNCH(true) : LY_RES_LAUNCH(false);
+#undef LY_RES_LAUNCH
 }

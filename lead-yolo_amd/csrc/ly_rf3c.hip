@@ -151,17 +151,8 @@ static size_t rc_stats_lds(int s, int TH, int TW) {
 template <typename T, int S, bool RAW>
 static int rc_launch_stats(const void* x, int ldx, int n_img, int H, int W, int C, int Ho, int Wo, int TH, int TW, int nct, int nrt, const float* wq,
                            float* mm, float* part, size_t lds, hipStream_t st) {
-  auto k = ly_rf3c_stats_kernel<T, S, RAW>;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
-  hipLaunchKernelGGL(k, dim3((unsigned)(n_img * nrt * nct)), dim3(LY_THREADS), lds, st, reinterpret_cast<const T*>(x), ldx, H, W, C, Ho, Wo, TH, TW, nct, nrt,
-                     wq, mm, part);
-  LY_LAUNCH_CHECK();
-  return 0;
+  return ly_launch_lds<ly_rf3c_stats_kernel<T, S, RAW>>(dim3((unsigned)(n_img * nrt * nct)), dim3(LY_THREADS), lds, st, reinterpret_cast<const T*>(x), ldx, H, W,
+                                                        C, Ho, Wo, TH, TW, nct, nrt, wq, mm, part);
 }
 
 extern "C" int ly_rf3c_stats(const void* x, int ldx, int n_img, int H, int W, int C, int s, const float* wq, int raw, int TH, int TW, float* mm,
@@ -174,7 +165,7 @@ extern "C" int ly_rf3c_stats(const void* x, int ldx, int n_img, int H, int W, in
   const int nct = (Wo + TW - 1) / TW, nrt = (Ho + TH - 1) / TH;
   LY_CHECK(!part || slices == nct * nrt, "rf3c_stats: the pooling partials are one row per tile: slices must be %d", nct * nrt);
   const size_t lds = rc_stats_lds(s, TH, TW);
-  LY_CHECK(lds <= 160 * 1024, "rf3c_stats: tile needs %zu B LDS", lds);
+  LY_CHECK(lds <= LY_LDS_MAX, "rf3c_stats: tile needs %zu B LDS", lds);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 #define RC_ST(T_, S_, R_) rc_launch_stats<T_, S_, R_>(x, ldx, n_img, H, W, C, Ho, Wo, TH, TW, nct, nrt, wq, mm, part, lds, st)
   if (dtype == LY_BF16) return s == 1 ? (raw ? RC_ST(__bf16, 1, true) : RC_ST(__bf16, 1, false)) : (raw ? RC_ST(__bf16, 2, true) : RC_ST(__bf16, 2, false));
@@ -428,19 +419,10 @@ static int rc_launch_fwd_s(const LyRfcbam3Params& P, const float* wq, hipStream_
   const int gy = (P.N + 16 * NW * MT - 1) / (16 * NW * MT);
   const int IH = P.s * (P.TH - 1) + 3, IW = P.s * (P.TW - 1) + 3;
   const size_t lds = sizeof(float) * ((size_t)IH * IW * RC_CB + RC_TP * 9) + (size_t)LyT<T>::PL * RC_KR * 128;
-  LY_CHECK(lds <= 160 * 1024, "rf3c_fwd: tile needs %zu B LDS", lds);
-  auto k = ly_rf3c_fwd_kernel<T, MT, NW, S, RAW>;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
+  LY_CHECK(lds <= LY_LDS_MAX, "rf3c_fwd: tile needs %zu B LDS", lds);
   const long nb = (long)P.n_img * nrt * nct * gy;
   LY_CHECK(nb < (1L << 31), "rf3c_fwd: grid too large");
-  hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(NW * 64), lds, st, P, wq, gy, nct, nrt);
-  LY_LAUNCH_CHECK();
-  return 0;
+  return ly_launch_lds<ly_rf3c_fwd_kernel<T, MT, NW, S, RAW>>(dim3((unsigned)nb), dim3(NW * 64), lds, st, P, wq, gy, nct, nrt);
 }
 
 template <typename T, int MT, int NW>

@@ -533,18 +533,9 @@ static int rb_launch(const LyRf3cBwdParams& P, hipStream_t st) {
   constexpr int O = 32 * KS;
   size_t lds = (size_t)IH * IW * RC_CB * 4 + RC_KR * 128 + RC_TP * (2 * O + 16) + (size_t)32 * 9 * (MODE == RB_A ? 2 : 8) * 4 + 64 * 4;
   if (MODE == RB_C) lds += ((size_t)IH * IW + IH + 2 * P.TW * nct + 2 + 27) * RC_CB * 4;
-  LY_CHECK(lds <= 160 * 1024, "rf3c_bwd: pass %d needs %zu B LDS for this shape (tile %dx%d, W = %d, O = %d)", MODE, lds, P.TH, P.TW, P.W, O);
-  auto k = ly_rf3c_bwd_kernel<MODE, KS>;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
+  LY_CHECK(lds <= LY_LDS_MAX, "rf3c_bwd: pass %d needs %zu B LDS for this shape (tile %dx%d, W = %d, O = %d)", MODE, lds, P.TH, P.TW, P.W, O);
   // (launched with the whole LDS of a CU: a block of this family must not share its CU with any other block, see ly_rf3c.hip)
-  hipLaunchKernelGGL(k, dim3((unsigned)(P.n_img * (P.C / RC_CB))), dim3(LY_THREADS), (size_t)(160 * 1024), st, P, nct, nrt);
-  LY_LAUNCH_CHECK();
-  return 0;
+  return ly_launch_lds<ly_rf3c_bwd_kernel<MODE, KS>>(dim3((unsigned)(P.n_img * (P.C / RC_CB))), dim3(LY_THREADS), LY_LDS_MAX, st, P, nct, nrt);
 }
 
 template <int MODE>
@@ -764,17 +755,9 @@ extern "C" int ly_rf3c_wgrad(const LyRf3cBwdParams* p, void* stream) {
   const int nog = (P.O + RW_OG - 1) / RW_OG;
   const int IH = 2 * (P.TH - 1) + 3, IW = 2 * (P.TW - 1) + 3;
   const size_t lds = (size_t)IH * IW * RC_CB * 4 + RC_KR * 128 + RC_TP * RW_RS + RC_TP * 9 * 4;
-  LY_CHECK(lds <= 160 * 1024, "rf3c_wgrad: tile needs %zu B LDS", lds);
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ly_rf3c_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
+  LY_CHECK(lds <= LY_LDS_MAX, "rf3c_wgrad: tile needs %zu B LDS", lds);
   const int ng = P.ng < P.n_img ? P.ng : P.n_img;
   LY_CHECK(ng == P.ng, "rf3c_wgrad: ng = %d exceeds the %d images", P.ng, P.n_img);
-  hipLaunchKernelGGL(ly_rf3c_wgrad_kernel, dim3((unsigned)(ng * nog * (P.C / RC_CB))), dim3(LY_THREADS), (size_t)(160 * 1024), reinterpret_cast<hipStream_t>(stream), P, nct,
-                     nrt, nog);
-  LY_LAUNCH_CHECK();
-  return 0;
+  return ly_launch_lds<ly_rf3c_wgrad_kernel>(dim3((unsigned)(ng * nog * (P.C / RC_CB))), dim3(LY_THREADS), LY_LDS_MAX, reinterpret_cast<hipStream_t>(stream), P, nct,
+                                             nrt, nog);
 }

@@ -392,31 +392,20 @@ static int rm_launch_fwd(const LyRfcbam3Params& P, hipStream_t st) {
   const int gy = P.N / (32 * MT);
   const int lds_x = (int)((RM_XTILE + (size_t)P.C * 4 + 63) / 64 * 64);
   const size_t lds = (size_t)2 * (2 * (RM_GF + 2 * MT) + MT) * 1024 + 2 * MT * 32 * 4 + RM_WAVES * (size_t)lds_x;
-  LY_CHECK(lds <= 160 * 1024, "rf3m_fwd: needs %zu B LDS", lds);
-  // development builds (make CXXFLAGS+=-DLY_RM_DEVEL) read LY_RM_PROF / LY_RM_DBG / LY_RM_SDBG: the profiling kernel and the timing-only ablations
-  // (wrong results by construction) are not reachable from the environment in the shipped library
-#ifdef LY_RM_DEVEL
-  static const bool prof = getenv("LY_RM_PROF") != nullptr;
-  auto k = prof ? ly_rf3m_fwd_kernel<MT, true> : ly_rf3m_fwd_kernel<MT, false>;
-#else
-  auto k = ly_rf3m_fwd_kernel<MT, false>;
-#endif
-  static LyDevOnce once;
-  if (once.need()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
+  LY_CHECK(lds <= LY_LDS_MAX, "rf3m_fwd: needs %zu B LDS", lds);
   const long tiles = (long)P.n_img * nrt * nct;
   const long nb = (tiles + RM_WAVES - 1) / RM_WAVES * gy;
   LY_CHECK(nb < (1L << 31), "rf3m_fwd: grid too large");
+  // development builds (make CXXFLAGS+=-DLY_RM_DEVEL) read LY_RM_PROF / LY_RM_DBG / LY_RM_SDBG: the profiling kernel and the timing-only ablations
+  // (wrong results by construction) are not reachable from the environment in the shipped library
 #ifdef LY_RM_DEVEL
   static const int dbg = getenv("LY_RM_DBG") ? atoi(getenv("LY_RM_DBG")) : 0;          // development: 1 = no weight copies (wrong results, timing only)
+  static const bool prof = getenv("LY_RM_PROF") != nullptr;
+  if (prof) return ly_launch_lds<ly_rf3m_fwd_kernel<MT, true>>(dim3((unsigned)nb), dim3(RM_THREADS), lds, st, P, nct, nrt, gy, lds_x, dbg);
 #else
   const int dbg = 0;
 #endif
-  hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(RM_THREADS), lds, st, P, nct, nrt, gy, lds_x, dbg);
-  LY_LAUNCH_CHECK();
-  return 0;
+  return ly_launch_lds<ly_rf3m_fwd_kernel<MT, false>>(dim3((unsigned)nb), dim3(RM_THREADS), lds, st, P, nct, nrt, gy, lds_x, dbg);
 }
 
 // P as for ly_rfcbam3_fwd with: dtype LY_BF16, stats == NULL, linear == 0 (inference form), P.wg ignored, TH*TW <= 32, and
@@ -606,27 +595,20 @@ extern "C" int ly_rf3m_stats(const void* x, int ldx, int n_img, int H, int W, in
   LY_CHECK(!part || slices == nct * nrt, "rf3m_stats: the pooling partials are one row per tile: slices must be %d", nct * nrt);
   const long tiles = (long)n_img * nrt * nct;
   const size_t lds = (size_t)2 * RM_UNITS * RM_GF * 1024 + RM_WAVES * (size_t)RM_XTILE;
-  auto k = ly_rf3m_stats_kernel<0>;
-  static LyDevOnce once;
-  bool need = once.need();
+#define RM_STATS(ABL_)                                                                                                                          \
+  ly_launch_lds<ly_rf3m_stats_kernel<ABL_>>(dim3((unsigned)((tiles + RM_WAVES - 1) / RM_WAVES)), dim3(RM_THREADS), lds, reinterpret_cast<hipStream_t>(stream), \
+                                            reinterpret_cast<const __bf16*>(x), ldx, n_img, H, W, C, Ho, Wo, s, TH, TW, nct, nrt, wst, mm, part)
 #ifdef LY_RM_DEVEL
   static const int sdbg = getenv("LY_RM_SDBG") ? atoi(getenv("LY_RM_SDBG")) : 0;     // development: ablations of the loop (timing only)
   switch (sdbg) {
-    case 1: k = ly_rf3m_stats_kernel<1>; break;
-    case 2: k = ly_rf3m_stats_kernel<2>; break;
-    case 4: k = ly_rf3m_stats_kernel<4>; break;
-    case 8: k = ly_rf3m_stats_kernel<8>; break;
-    case 15: k = ly_rf3m_stats_kernel<15>; break;
+    case 1: return RM_STATS(1);
+    case 2: return RM_STATS(2);
+    case 4: return RM_STATS(4);
+    case 8: return RM_STATS(8);
+    case 15: return RM_STATS(15);
     default: break;
   }
-  if (sdbg) need = true;
 #endif
-  if (need) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
-  hipLaunchKernelGGL(k, dim3((unsigned)((tiles + RM_WAVES - 1) / RM_WAVES)), dim3(RM_THREADS), lds, reinterpret_cast<hipStream_t>(stream),
-                     reinterpret_cast<const __bf16*>(x), ldx, n_img, H, W, C, Ho, Wo, s, TH, TW, nct, nrt, wst, mm, part);
-  LY_LAUNCH_CHECK();
-  return 0;
+  return RM_STATS(0);
+#undef RM_STATS
 }

@@ -284,22 +284,12 @@ static int launch_rf3_k(const LyRfcbam3Params& P, hipStream_t st) {
   const int gy = (P.N + 64 * MT - 1) / (64 * MT);
   const int IH = P.s * (P.TH - 1) + 3, IW = P.s * (P.TW - 1) + 3;
   size_t lds = LyT<T>::PL * (size_t)64 * LY_RSG + sizeof(float) * ((size_t)(SW ? 0 : 4 * LY_RF3_WF) + (size_t)IH * IW * (LY_GCC + 1));
-  LY_CHECK(lds <= 160 * 1024, "rfcbam3: tile needs %zu B LDS", lds);
+  LY_CHECK(lds <= LY_LDS_MAX, "rfcbam3: tile needs %zu B LDS", lds);
   LY_CHECK(IH * IW * (LY_GCC / 4) <= LY_RF3_NV * LY_THREADS, "rfcbam3: input tile %dx%d exceeds the staging capacity", IH, IW);
-  void (*k)(const LyRfcbam3Params, int, int, int);
-  if constexpr (SW) k = ly_rfcbam3_sw_kernel<T, MT>;
-  else k = ly_rfcbam3_kernel<T, MT>;
-  static bool configured = false;
-  if (!configured) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LY_CHECK(e == hipSuccess, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    configured = true;
-  }
   long nb = (long)P.n_img * nrt * nct * gy;
   LY_CHECK(nb < (1L << 31), "rfcbam3: grid too large");
-  hipLaunchKernelGGL(k, dim3((unsigned)nb), dim3(LY_THREADS), lds, st, P, gy, nct, nrt);
-  LY_LAUNCH_CHECK();
-  return 0;
+  if constexpr (SW) return ly_launch_lds<ly_rfcbam3_sw_kernel<T, MT>>(dim3((unsigned)nb), dim3(LY_THREADS), lds, st, P, gy, nct, nrt);
+  else return ly_launch_lds<ly_rfcbam3_kernel<T, MT>>(dim3((unsigned)nb), dim3(LY_THREADS), lds, st, P, gy, nct, nrt);
 }
 
 template <typename T, int MT>

@@ -693,18 +693,9 @@ extern "C" int ly_rf_bwd_dx(int n_img, int H, int W, int C, int k, int s, const 
       const int tiles_y = (Ho + TM - 1) / TM, tiles_x = (Wo + TM - 1) / TM;
       const size_t lds = (size_t)(TM + 1) * (TM + 1) * 9 * 64 * sizeof(T);
       const dim3 grid((unsigned)(n_img * tiles_y * tiles_x), (unsigned)((C + 63) / 64));
-      if (addnc) {
-        static bool a1 = false;
-        if (!a1) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_rf_bwd_dx_s2t_kernel<T, TM, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); a1 = true; }
-        hipLaunchKernelGGL((ly_rf_bwd_dx_s2t_kernel<T, TM, 1>), grid, dim3(LY_THREADS), lds, st, g, RF_CT(dug), wg, RF_T(dx), lddx, addnc, add_scale, tiles_y, tiles_x);
-      } else {
-        static bool a0 = false;
-        if (!a0) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ly_rf_bwd_dx_s2t_kernel<T, TM, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); a0 = true; }
-        hipLaunchKernelGGL((ly_rf_bwd_dx_s2t_kernel<T, TM, 0>), grid, dim3(LY_THREADS), lds, st, g, RF_CT(dug), wg, RF_T(dx), lddx, addnc, add_scale, tiles_y, tiles_x);
-      }
+      if (addnc) return ly_launch_lds<ly_rf_bwd_dx_s2t_kernel<T, TM, 1>>(grid, dim3(LY_THREADS), lds, st, g, RF_CT(dug), wg, RF_T(dx), lddx, addnc, add_scale, tiles_y, tiles_x);
+      return ly_launch_lds<ly_rf_bwd_dx_s2t_kernel<T, TM, 0>>(grid, dim3(LY_THREADS), lds, st, g, RF_CT(dug), wg, RF_T(dx), lddx, addnc, add_scale, tiles_y, tiles_x);
     });
-    LY_LAUNCH_CHECK();
-    return 0;
   }
   const int add = !addnc ? 0 : (g.chunk <= (long)H * W ? 2 : 1);
 #define RF_DX(KV, AV) hipLaunchKernelGGL((ly_rf_bwd_dx_kernel<T, KV, AV>), dim3(gx, gy), dim3(LY_THREADS), 0, st, g, RF_CT(dug), wg, RF_T(dx), lddx, addnc, add_scale)

@@ -14,6 +14,7 @@
 // LDS: du tile [64 px][160 B] (128 B data + 32: the 8 pixel rows x 32 B of a half-wave read hit all 64 banks) | halo [100][96 B] (64 + 32).
 #include "ly_tile.hpp"
 #include "ly_params.h"
+#include "ly_wgrad.hpp"
 #include <stdlib.h>
 
 #define W3_BN 64
@@ -196,10 +197,8 @@ __global__ __launch_bounds__(LY_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
 // block = 64 consecutive slab columns x 16 chunk lanes; grid.x covers the n_c * n_n * 64 * 288 / 64 column groups of one chunk
 __global__ __launch_bounds__(1024) void ly_wgrad3_combine_kernel(const LyWgradParams P, const float* __restrict__ slab, const int chunks, const int n_n,
                                                                 const int n_c, const int rls) {
-  __shared__ float red[16][64];                            // rls row lanes walk the chunks (see ly_wgrad_combine_body, ly_backward.hip)
-  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const long E = (long)n_c * n_n * (W3_BN * 288);
-  const long e = (long)blockIdx.x * 64 + cl;
+  const long e = (long)blockIdx.x * 64 + (threadIdx.x & 63);
   // decode (all lanes of the block share combo and row: 288 = 4.5 * 64, so a 64-column group may straddle two rows — decode per lane)
   const int combo = (int)(e / (W3_BN * 288));
   const int rem = (int)(e - (long)combo * (W3_BN * 288));
@@ -209,37 +208,7 @@ __global__ __launch_bounds__(1024) void ly_wgrad3_combine_kernel(const LyWgradPa
   const int orow = cn * W3_BN + row;
   const int cch = cc * W3_CK + (ct & 1) * 16 + li;
   const bool live = e < E && orow < P.n_valid && cch < P.c_valid;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (live) {
-    const float* p = slab + e;                               // four loads in flight per lane (see ly_wgrad_combine_kernel)
-    int c = rl;
-    for (; c + 7 * rls < chunks; c += 8 * rls) {        // eight loads fenced ahead of the adds (the scheduler sinks them back otherwise)
-      float v[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = p[(long)(c + rls * k) * E];
-      __builtin_amdgcn_sched_barrier(0);
-      a0 += v[0]; a1 += v[1]; a2 += v[2]; a3 += v[3];
-      a0 += v[4]; a1 += v[5]; a2 += v[6]; a3 += v[7];
-    }
-    for (; c + 3 * rls < chunks; c += 4 * rls) {
-      float v[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = p[(long)(c + rls * k) * E];
-      __builtin_amdgcn_sched_barrier(0);
-      a0 += v[0]; a1 += v[1]; a2 += v[2]; a3 += v[3];
-    }
-    if (c < chunks) a0 += p[(long)c * E];
-    if (c + rls < chunks) a1 += p[(long)(c + rls) * E];
-    if (c + 2 * rls < chunks) a2 += p[(long)(c + 2 * rls) * E];
-  }
-  red[rl][cl] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (rl == 0 && live) {
-    float s = 0.f;
-    for (int i = 0; i < rls; ++i) s += red[i][cl];
-    float* d = P.dw + (long)orow * P.lddw + (long)(ct >> 1) * P.dw_ts + (long)cch * P.dw_cs;
-    *d += s;
-  }
+  ly_wgrad_fold(slab + e, E, chunks, rls, live, P.dw + (long)orow * P.lddw + (long)(ct >> 1) * P.dw_ts + (long)cch * P.dw_cs);
 }
 
 // true when the problem is one this kernel takes (bf16, 3x3, stride 1, pad 1, NHWC, 16-byte friendly widths and pointers)

@@ -1192,6 +1192,53 @@ def test_wgrad3_halo_kernel(n, h, w, cin, cout, cvalid, ldx):
     assert float((got[1] - got[0]).abs().max()) <= 5e-4 * scale
 
 
+def test_large_lds_kernels_on_two_devices_of_one_process():
+    """Kernels whose dynamic LDS exceeds the 64 KB a launch gets by default, launched on device 0 and then on device 1 from ONE process
+    (skipped on a one-GPU box): the cap is a per-device function attribute (ly_launch_lds, csrc/ly_common.hpp), so the second device needs
+    it set as well; a refused launch is the library's error return.  By the launchers' own formulas:
+      * ops.wgrad, plain-row 1x1, N = 128, Cin = 128, M = 2 * 16 * 16: the 128 x 128 tile of launch_wgrad_tiled (csrc/ly_backward.hip),
+        one LDS buffer of PL * (PX / 8) rows of (128 + 128 + 16) * 16 B + 2 * 128 floats = 70,656 B for bf16 (PL 1, PX 128) and the same
+        70,656 B for fp32 (PL 2, PX 64);
+      * Conv k = 3, fp32, 128 -> 128 channels on 2 x 16 x 16 (ops.conv3x3, launch_conv3 in csrc/ly_conv3x3.hip): patch 16 x 8
+        (pick_conv_tile), row pitch 640 B, plane stride 18 * 640 = 11,520 B, PL * 4 planes = 92,160 B.
+    Each result against the fp64 contraction on the host with the tolerance of the op's single-device test: 2e-3 of the reference's
+    maximum for the bf16 weight gradient (test_wgrad3_halo_kernel), 1e-3 for fp32 (test_wgrad_x_prologue), 2^-14 * sum |w x| for the fp32
+    3x3 convolution (test_bf16x3_adversarial_bounds, tests/test_gpu_modules.py)."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs >= 2 GPUs")
+    import torch.nn.functional as F
+    import lead_yolo_amd as L
+    from lead_yolo_amd import ops
+    g = torch.Generator().manual_seed(11)
+    n, h, w, N, C = 2, 16, 16, 128, 128
+    m = n * h * w
+    wg = {}
+    for dtype in (torch.bfloat16, torch.float32):
+        du, x = torch.randn(m, N, generator=g).to(dtype), torch.randn(m, C, generator=g).to(dtype)
+        wg[dtype] = (du, x, du.double().t() @ x.double())
+    conv = L.Conv(C, N, 3, 1)
+    with torch.no_grad():
+        conv.conv.weight.copy_(0.05 * torch.randn(N, C, 3, 3, generator=g))
+        conv.bn.weight.fill_(1.0); conv.bn.bias.zero_(); conv.bn.running_mean.zero_(); conv.bn.running_var.fill_(1.0)
+        conv.bn.eps = 0.0
+        conv.act = torch.nn.Identity()
+        xc = torch.randn(n, C, h, w, generator=g)
+        want_c = F.conv2d(xc.double(), conv.conv.weight.double(), padding=1)
+        mag_c = F.conv2d(xc.abs().double(), conv.conv.weight.abs().double(), padding=1)         # sum_k |w_k x_k|
+    for d in (0, 1):
+        dev = torch.device("cuda", d)
+        with torch.cuda.device(d):
+            for dtype, (du, x, want) in wg.items():
+                dw = torch.zeros(N, C, dtype=torch.float32, device=dev)
+                ops.wgrad(M=m, H=h, W=w, N=N, du=du.to(dev), lddu=N, x=x.to(dev), ldx=C, Hin=h, Win=w, Cin=C, dw=dw, lddw=C)
+                torch.cuda.synchronize()
+                err, scale = float((dw.cpu().double() - want).abs().max()), float(want.abs().max())
+                assert err <= (2e-3 if dtype == torch.bfloat16 else 1e-3) * scale, (d, dtype, err, scale)
+            with torch.no_grad():
+                got = copy.deepcopy(conv).to(dev).eval()(xc.to(dev)).double().cpu()
+            assert bool(((got - want_c).abs() <= 2.0 ** -14 * mag_c + 1e-7).all()), (d, float(((got - want_c).abs() / mag_c).max()))
+
+
 def _pack_plain(w, dtype):
     """packed fragment image of a [N, K] fp32 matrix (pack.packed over a parameter-like tensor)"""
     from lead_yolo_amd import ops, pack
