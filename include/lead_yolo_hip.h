@@ -20,7 +20,8 @@ extern "C" {
 
 enum { LY_F32 = 0, LY_BF16 = 1 };
 int ly_abi_version(void);      /* 5: ly_mosaic_img / ly_mosaic_labels (4: augmented inference, 3: ly_adam_step, 2: dtype-polymorphic entry points);
-                                * added since, version unchanged (new symbols only): LyMixup, ly_mosaic_mix_img, ly_mosaic_mix_labels */
+                                * added since, version unchanged (new symbols only): LyMixup, ly_mosaic_mix_img, ly_mosaic_mix_labels,
+                                * ly_resize_u8 */
 const char* ly_last_error(void);
 
 /* FasterNet MLPBlock forward, eval form (BN folded to scale/shift):
@@ -315,6 +316,14 @@ typedef struct LyScaleImgSpec {
   int flip;               /* != 0: resample x.flip(3)                                                 */
 } LyScaleImgSpec;
 int ly_scale_img(const void* x /*T*/, int n_img, int C, int H, int W, const LyScaleImgSpec* specs, int nspec, float pad, int dtype, void* stream);
+
+/* Multi-scale training (train.py --multi-scale, csrc/ly_augment.hip): the uint8 batch resized for one optimisation step,
+ *   out = F.interpolate(x.float() / 255, size=(Ho, Wo), mode='bilinear', align_corners=False),
+ * in one launch, with ly_scale_img's index arithmetic (one shared device function); the fp32 copy of the source never exists.  fp32 output
+ * only (the train-mode patch embedding reads the image as fp32).  Wo must be a multiple of 4, out 16-byte aligned, source and output
+ * each below 2^31 elements.                                                                                                              */
+int ly_resize_u8(const unsigned char* x /*[n,C,H,W]*/, int n_img, int C, int H, int W,
+                 float* out /*[n,C,Ho,Wo]*/, int Ho, int Wo, void* stream);
 
 /* ---- training augmentation on the device (csrc/ly_mosaic.hip; utils/dataloaders.py LoadImagesAndLabels.__getitem__ with augment=True) ----
  * The image bank holds every training image as load_image returns it (uint8 HWC BGR, long side resized) back to back; a tile addresses one

@@ -7,7 +7,8 @@ from .modules import Lazy  # noqa: F401
 from .model import DEFAULT_CFG, DetectionModel, Model, load_cfg, make_divisible, parse_model  # noqa: F401
 from .loss import ComputeLoss  # noqa: F401
 from .ddp import GradReducer  # noqa: F401
-from .train import GraphedTrainStep, ModelEMA, forward_backward, freeze_layers, optimizer_step, smart_optimizer, train_step  # noqa: F401
+from .train import (GraphedTrainStep, ModelEMA, MultiScaleTrainStep, forward_backward, freeze_layers, multi_scale_shape, multi_scale_size,  # noqa: F401
+                    optimizer_step, smart_optimizer, train_step)
 from .optim import FusedAdam, FusedAdamW, FusedSGD  # noqa: F401
 from .graph import GraphedForward  # noqa: F401
 from .nms import nms_padded, non_max_suppression  # noqa: F401,E402

@@ -679,6 +679,29 @@ def scale_img(x, specs, pad=SCALE_IMG_PAD):
     return outs
 
 
+def resize_u8(x, size, out=None):
+    """The resized batch of a multi-scale training step in ONE launch (ly_resize_u8): x uint8 NCHW [n, c, h, w] ->
+    F.interpolate(x.float() / 255, size=size, mode='bilinear', align_corners=False), float32 contiguous NCHW; `size` = (ho, wo), wo a
+    multiple of 4.  `out` (float32 [n, c, ho, wo], contiguous): written in place of a new tensor — the input buffer of a captured graph."""
+    if not x.is_cuda:
+        raise RuntimeError(f"resize_u8: the HIP path needs a CUDA/ROCm tensor (got {x.device}); there is no CPU fallback")
+    if x.dtype != torch.uint8 or x.dim() != 4:
+        raise TypeError(f"resize_u8: a uint8 NCHW image batch expected (got {x.dtype}, {tuple(x.shape)})")
+    x = x.contiguous()
+    n, c, h, w = x.shape
+    ho, wo = (int(s) for s in size)
+    if out is None:
+        if ho <= 0 or wo <= 0 or n * c * ho * wo >= 1 << 31:
+            raise ValueError(f"resize_u8: cannot resize {tuple(x.shape)} to {ho} x {wo}")
+        out = torch.empty((n, c, ho, wo), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, c, ho, wo) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"resize_u8: out must be a contiguous float32 {(n, c, ho, wo)} tensor on {x.device} (got {out.dtype}, {tuple(out.shape)})")
+    # algorithmic bytes: the source once, every output element once
+    with _Timed("ly_resize_u8_kernel", 0.0, 1.0 * n * c * h * w + 4.0 * n * c * ho * wo):
+        capi.check(capi.lib().ly_resize_u8(_p(x), n, c, h, w, _p(out), ho, wo, capi.stream_ptr()), "ly_resize_u8")
+    return out
+
+
 def detect_head_bwd(dp, n, h, w, na, no, du, ldu, dbias):
     """dp fp32 [n, na, h, w, no] -> du rows [n*h*w, ldu] (columns >= na*no zero), dbias[na*no] += column sums (dbias fp32, or a float64
     scratch of small_grad_scratch)"""

@@ -12,6 +12,7 @@ torch.optim object.
 import ctypes
 import math
 import os
+import random
 import sys
 from copy import deepcopy
 
@@ -107,8 +108,35 @@ class ModelEMA:
                     v.mul_(d).add_(msd[k].detach(), alpha=1 - d)
 
 
-def forward_backward(model, compute_loss, imgs, targets, world_size=1, amp=None):
-    """uint8 / float batch -> train-mode forward -> loss -> backward; gradients land in `.grad` (train.py:295-324)"""
+def multi_scale_size(imgsz, gs=32, rng=random):
+    """The reference's `--multi-scale` draw (train.py:309): a size between 0.5x and 1.5x of imgsz, a multiple of the grid size gs.  Exactly
+    one `randrange` call on `rng` (Python's `random` module or a random.Random): a seeded run draws the reference's sequence."""
+    return rng.randrange(int(imgsz * 0.5), int(imgsz * 1.5) + gs) // gs * gs
+
+
+def multi_scale_shape(shape, sz, gs=32):
+    """(h, w) of a batch of shape (h, w) resized for the drawn size sz (train.py:310-312): the long side becomes sz, each side is rounded up
+    to a multiple of gs; the batch's own shape when the scale factor is 1."""
+    h, w = (int(v) for v in shape)
+    sf = sz / max(h, w)
+    if sf == 1:
+        return h, w
+    return tuple(math.ceil(x * sf / gs) * gs for x in (h, w))
+
+
+def _img_size(img_size):
+    return (int(img_size),) * 2 if isinstance(img_size, int) else tuple(int(v) for v in img_size)
+
+
+def forward_backward(model, compute_loss, imgs, targets, world_size=1, amp=None, img_size=None):
+    """uint8 / float batch -> train-mode forward -> loss -> backward; gradients land in `.grad` (train.py:295-324).
+    img_size = (h, w) (or one int) other than the batch's own size: the uint8 batch is first resized to it on the device
+    (ops.resize_u8, the reference's `--multi-scale` interpolate) and the model takes the float result."""
+    if img_size is not None and _img_size(img_size) != tuple(imgs.shape[2:]):
+        if imgs.dtype != torch.uint8:
+            raise ValueError(f"forward_backward: img_size={_img_size(img_size)} resizes a uint8 batch (got {imgs.dtype} {tuple(imgs.shape)}); "
+                             "resize a float batch before the step")
+        imgs = ops.resize_u8(imgs, _img_size(img_size))
     if imgs.dtype == torch.uint8 and not getattr(model, "u8_input", False):
         imgs = imgs.float() / 255           # (a model whose first layer is the HIP patch embedding takes the uint8 batch as it is)
     ops.stats_pool_begin(imgs.device)       # one zero fill for all BatchNorm accumulators of the step (ops._StatsPool)
@@ -162,15 +190,16 @@ def _set_deferred_average(optimizer, reducer):
             optimizer.grad_scale = 1.0
 
 
-def train_step(model, compute_loss, optimizer, imgs, targets, ema=None, reducer=None, world_size=1, max_norm=10.0, amp=None):
+def train_step(model, compute_loss, optimizer, imgs, targets, ema=None, reducer=None, world_size=1, max_norm=10.0, amp=None, img_size=None):
     """One optimisation step; imgs uint8 or float [B,3,H,W] on the model's device, targets [n,6].
     amp: None (fp32 storage) or torch.bfloat16 — forward and loss run inside torch.autocast(dtype=amp), the reference's
     `with torch.cuda.amp.autocast(amp)` region (train.py:316) with bf16 in place of fp16 (no GradScaler needed: bf16 keeps
-    fp32's exponent range).  Returns (loss, loss_items) as detached device tensors (no host sync)."""
+    fp32's exponent range).  img_size: the multi-scale size of this step, see forward_backward.
+    Returns (loss, loss_items) as detached device tensors (no host sync)."""
     _set_deferred_average(optimizer, reducer)
     if reducer is not None:
         reducer.reset()
-    loss, items = forward_backward(model, compute_loss, imgs, targets, world_size=world_size, amp=amp)
+    loss, items = forward_backward(model, compute_loss, imgs, targets, world_size=world_size, amp=amp, img_size=img_size)
     if reducer is not None:
         reducer.wait()
     optimizer_step(model, optimizer, ema=ema, max_norm=max_norm, reducer=reducer)
@@ -215,15 +244,26 @@ class GraphedTrainStep:
     eager work of a step.  Serial: graph A -> one all-reduce of the reducer's master buffer issued from the step's stream -> graph B.
 
     accumulate = k (the reference's gradient accumulation, train.py:157,300,330): call k times with k micro-batches; graph A runs every
-    time (gradients add up in place), the exchange and graph B only on every k-th call, which returns `stepped = True` in `.stepped`."""
+    time (gradients add up in place), the exchange and graph B only on every k-th call, which returns `stepped = True` in `.stepped`.
+
+    img_size = (h, w) other than the batch's own size (multi-scale training, MultiScaleTrainStep): the graph's first node is the resize
+    (ops.resize_u8); the input buffer stays the uint8 batch at its own size.  buffers = (imgs, targets): the step reads these tensors
+    instead of clones of the batch (several steps fed through one pair of buffers).  pool: capture into this memory pool
+    (torch.cuda.graph_pool_handle() / another graph's .pool()) instead of a private one."""
 
     def __init__(self, model, compute_loss, optimizer, imgs, targets, ema=None, amp=None, max_norm=10.0, warmup=3, reducer=None, world_size=1,
-                 accumulate=1, dp_exchange=None):
+                 accumulate=1, dp_exchange=None, img_size=None, buffers=None, pool=None):
         if not getattr(optimizer, "fused", False):
             raise NotImplementedError("GraphedTrainStep needs a fused optimiser (smart_optimizer(..., fused=True)): the torch.optim objects + "
                                       "clip_grad_norm_ keep per-step host state")
         from . import capi, pack
-        self.imgs, self.targets = imgs.clone(), targets.clone()
+        if buffers is None:
+            self.imgs, self.targets = imgs.clone(), targets.clone()
+        else:
+            self.imgs, self.targets = buffers
+            self._load(imgs, targets)
+        self.img_size = _img_size(img_size) if img_size is not None else tuple(imgs.shape[2:])
+        self._pool = pool
         self.model, self.optimizer, self.ema, self.reducer, self.max_norm = model, optimizer, ema, reducer, max_norm
         self.accumulate, self._micro, self.stepped = max(int(accumulate), 1), 0, False
         self.probe = None
@@ -232,7 +272,7 @@ class GraphedTrainStep:
             raise ValueError(f"GraphedTrainStep: dp_exchange must be 'probe', 'serial' or 'overlapped' (got {self.dp_exchange!r})")
         self.dp_probe = None                   # dict(serial_ms, overlapped_ms, chosen, ranks, replays) once both forms were timed
         self._serial = False
-        args = dict(ema=ema, amp=amp, max_norm=max_norm, reducer=reducer, world_size=world_size)
+        args = dict(ema=ema, amp=amp, max_norm=max_norm, reducer=reducer, world_size=world_size, img_size=self.img_size)
         cur = torch.cuda.current_stream()
         side = torch.cuda.Stream(device=imgs.device)
         side.wait_stream(cur)
@@ -279,8 +319,9 @@ class GraphedTrainStep:
     def _capture(self, model, compute_loss, optimizer, ema, amp, max_norm, reducer, world_size, capi):
         imgs = self.imgs
         if reducer is None and self.accumulate == 1 and not SPLIT_GRAPHS:
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self.loss, self.items = train_step(model, compute_loss, optimizer, self.imgs, self.targets, ema=ema, amp=amp, max_norm=max_norm)
+            with torch.cuda.graph(self.graph, pool=self._pool, capture_error_mode="thread_local"):
+                self.loss, self.items = train_step(model, compute_loss, optimizer, self.imgs, self.targets, ema=ema, amp=amp, max_norm=max_norm,
+                                                   img_size=self.img_size)
         else:
             lib = capi.lib()
             mark = None
@@ -305,10 +346,10 @@ class GraphedTrainStep:
                     if len(reducer._mark_order) % stride == stride - 1:
                         capi.check(lib.ly_event_record(self._events[bi], capi.stream_ptr()), "ly_event_record")
                         self._recorded.add(bi)
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+            with torch.cuda.graph(self.graph, pool=self._pool, capture_error_mode="thread_local"):
                 if reducer is not None:
                     reducer.begin_marks(mark)
-                self.loss, self.items = forward_backward(model, compute_loss, self.imgs, self.targets, world_size=world_size, amp=amp)
+                self.loss, self.items = forward_backward(model, compute_loss, self.imgs, self.targets, world_size=world_size, amp=amp, img_size=self.img_size)
                 if reducer is not None:
                     self._marked, self._unmarked = reducer.end_marks()
             self.opt_graph = torch.cuda.CUDAGraph()
@@ -395,13 +436,13 @@ class GraphedTrainStep:
     def _load(self, imgs, targets):
         if imgs is not None and imgs.data_ptr() != self.imgs.data_ptr():
             if imgs.dtype != self.imgs.dtype or tuple(imgs.shape) != tuple(self.imgs.shape):
-                raise ValueError(f"GraphedTrainStep: the batch must keep the captured dtype and shape {self.imgs.dtype} {tuple(self.imgs.shape)} "
+                raise ValueError(f"{type(self).__name__}: the batch must keep the captured dtype and shape {self.imgs.dtype} {tuple(self.imgs.shape)} "
                                  f"(got {imgs.dtype} {tuple(imgs.shape)}); a float [0, 1] batch copied into the captured uint8 buffer would "
                                  "truncate to zeros")
             self.imgs.copy_(imgs, non_blocking=True)
         if targets is not None and targets.data_ptr() != self.targets.data_ptr():
             if tuple(targets.shape) != tuple(self.targets.shape) or targets.dtype != self.targets.dtype:
-                raise ValueError(f"GraphedTrainStep: targets must keep the captured shape {tuple(self.targets.shape)} (pad with rows whose "
+                raise ValueError(f"{type(self).__name__}: targets must keep the captured shape {tuple(self.targets.shape)} (pad with rows whose "
                                  f"image index is -1), got {tuple(targets.shape)} {targets.dtype}")
             self.targets.copy_(targets, non_blocking=True)
 
@@ -488,3 +529,104 @@ class GraphedTrainStep:
         if self.ema is not None:
             self.ema.updates += 1
         return self.loss, self.items
+
+
+class MultiScaleTrainStep:
+    """The captured optimisation step under the reference's `--multi-scale` (train.py:308-313): every call resizes the uint8 batch to a size
+    between 0.5x and 1.5x of `img_size` (a multiple of the grid size `gs`) on the device and trains at that size.
+
+        step = MultiScaleTrainStep(model, compute_loss, optimizer, imgs, targets, ema=ema, amp=torch.bfloat16, img_size=640, gs=32, seed=0)
+        loss, items = step(imgs, targets)            # draws the size as the reference does (multi_scale_size); step.last_size tells
+        loss, items = step(imgs, targets, size=sz)   # or takes it from the caller (a loop that owns the RNG); draws nothing
+
+    One uint8 batch buffer and one target buffer (`.imgs`, `.targets`) serve every size: MosaicAugment(..., out=(step.imgs, step.targets))
+    feeds them.  Every distinct resized shape (multi_scale_shape) gets its own GraphedTrainStep whose first node is the resize, captured at
+    the first use of that shape; `.graphed_sizes` lists them in capture order.  Construction captures the batch's own shape and, like
+    GraphedTrainStep, runs `warmup` real steps on the given batch.  A capture in the middle of training leaves no trace: the model state,
+    the EMA, the optimiser's device state and `ema.updates` are saved before its warm-up steps and put back after the capture.
+
+    The graphs share ONE memory pool: replays are serialised on one stream and no graph reads what another one left in the pool, so the
+    reserved memory is about that of the largest size, not the sum over sizes.  Once `max_graphs` shapes are captured (None: no limit),
+    further shapes run the eager train_step(..., img_size=): correct, at eager speed.
+
+    seed: None draws from Python's `random` module (the reference's generator), a number from a private random.Random(seed).
+    A reducer or accumulate > 1 is refused: in the reference every rank draws its own size, so the ranks' graphs differ from step to step."""
+
+    def __init__(self, model, compute_loss, optimizer, imgs, targets, ema=None, amp=None, max_norm=10.0, warmup=3, img_size=None, gs=32, seed=None,
+                 max_graphs=None, reducer=None, accumulate=1):
+        if reducer is not None:
+            raise NotImplementedError("MultiScaleTrainStep: data-parallel multi-scale graphs are not built (every rank draws its own size); "
+                                      "use the eager train_step(..., img_size=, reducer=)")
+        if int(accumulate) != 1:
+            raise NotImplementedError("MultiScaleTrainStep: accumulate > 1 is not built; use the eager train_step(..., img_size=)")
+        if imgs.dtype != torch.uint8 or imgs.dim() != 4:
+            raise ValueError(f"MultiScaleTrainStep: a uint8 [B, 3, H, W] batch expected (got {imgs.dtype} {tuple(imgs.shape)})")
+        self.model, self.compute_loss, self.optimizer, self.ema = model, compute_loss, optimizer, ema
+        self._args = dict(ema=ema, amp=amp, max_norm=max_norm)
+        self.warmup = warmup
+        self.imgs, self.targets = imgs.clone(), targets.clone()
+        self.img_size = int(img_size) if img_size is not None else max(imgs.shape[2:])
+        self.gs, self.max_graphs = int(gs), max_graphs
+        self.rng = random if seed is None else random.Random(seed)
+        self.last_size = None
+        self._steps = {}                       # resized (h, w) -> GraphedTrainStep, in capture order
+        self._pool = torch.cuda.graph_pool_handle()
+        if max_graphs is None or max_graphs > 0:
+            self._capture(tuple(imgs.shape[2:]), keep_state=False)
+
+    _load = GraphedTrainStep._load
+
+    @property
+    def graphed_sizes(self):
+        return list(self._steps)
+
+    def _capture(self, shape, keep_state=True):
+        from . import pack
+
+        def state():
+            ts = list(self.model.state_dict().values()) + (list(self.ema.ema.state_dict().values()) if self.ema is not None else [])
+            return ts + self.optimizer.device_state()
+        if keep_state:
+            # the warm-up steps of a GraphedTrainStep are real optimisation steps: put everything they change back (as the exchange probe does)
+            table = self.optimizer._table
+            saved = [t.clone() for t in state()]
+            updates = self.ema.updates if self.ema is not None else 0
+        step = GraphedTrainStep(self.model, self.compute_loss, self.optimizer, self.imgs, self.targets, warmup=self.warmup, img_size=shape,
+                                buffers=(self.imgs, self.targets), pool=self._pool, **self._args)
+        if keep_state:
+            if self.optimizer._table is not table:
+                raise RuntimeError("MultiScaleTrainStep: the optimiser rebuilt its tensor table during a capture (parameters, gradients or the EMA "
+                                   "were replaced since the last step): its state cannot be put back — build a new MultiScaleTrainStep")
+            with torch.no_grad():
+                for dst, src in zip(state(), saved):
+                    dst.copy_(src)
+            if self.ema is not None:
+                self.ema.updates = updates
+            self.optimizer._table["lrs"] = None        # `hyper` is the saved one again: the next step writes the host-set scalars anew
+            pack.touch_weights()
+        self._steps[shape] = step
+        return step
+
+    def _shape(self, size):
+        if int(size) != size or size <= 0 or size % self.gs:
+            raise ValueError(f"MultiScaleTrainStep: size must be a positive multiple of the grid size {self.gs} (got {size})")
+        return multi_scale_shape(self.imgs.shape[2:], int(size), self.gs)
+
+    def capture(self, size):
+        """Capture the step of `size` now, on the batch in the buffers, without training on it (the state is put back).  The pool grows by
+        what a size needs beyond the blocks earlier captures left free, so capturing the LARGEST size first keeps the reserved memory lowest
+        (tools/multiscale_bench.py measures both orders).  -> whether the size is captured (False: max_graphs reached)."""
+        shape = self._shape(size)
+        if shape not in self._steps and (self.max_graphs is None or len(self._steps) < self.max_graphs):
+            self._capture(shape)
+        return shape in self._steps
+
+    def __call__(self, imgs=None, targets=None, size=None):
+        if size is None:
+            size = multi_scale_size(self.img_size, self.gs, self.rng)
+        shape = self._shape(size)
+        self._load(imgs, targets)
+        self.last_size = int(size)
+        if self.capture(size):
+            return self._steps[shape]()
+        return train_step(self.model, self.compute_loss, self.optimizer, self.imgs, self.targets, img_size=shape, **self._args)
