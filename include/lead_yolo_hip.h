@@ -562,6 +562,9 @@ int ly_wgrad_group(const LyWgradParams* arr, int n, void* stream);
 /* development switch (returns the previous value): 0 sends 3x3 / stride-1 bf16 problems to the generic tiled kernel instead of the halo-tile
  * kernel of csrc/ly_wgrad3.hip (A/B timing and the equivalence test); default 1.                                                           */
 int ly_tune_wgrad3(int on);
+/* development switch (returns the previous value): 0 sends plain-row 1x1 bf16 problems with 16-byte friendly widths to the register-transposing
+ * tiled kernel instead of the transposed-read kernel of csrc/ly_wgrad1.hip (A/B timing and the equivalence test); default 1.               */
+int ly_tune_wgrad1(int on);
 
 /* Adjoint of the nearest-2x read: out[n,h,w,:] = sum of d[n, 2h+{0,1}, 2w+{0,1}, :]  (d is a 2Hs x 2Ws map).      */
 int ly_up2_bwd(const void* d /*T*/, int ldd, int n_img, int Hs, int Ws, int C, void* out /*T*/, int ldo, int dtype, void* stream);

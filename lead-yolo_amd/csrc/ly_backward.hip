@@ -925,16 +925,7 @@ __global__ __launch_bounds__(LY_THREADS) __attribute__((amdgpu_waves_per_eu(BN +
 
 // Several independent weight gradients of ONE tile class in one launch (ly_wgrad_group): the problems share the ~512 blocks, so each block
 // walks a longer pixel chunk — the fixed cost of a block (first-load latency, the atomic flush of its 64 KB tile) is paid half / a third as
-// often per pixel, and the launch fills the chip where a lone small problem leaves a ragged second wave.
-#define LY_WGRAD_GROUP_MAX 4
-struct LyWgradGroupArgs {
-  LyWgradParams p[LY_WGRAD_GROUP_MAX];
-  long chunk_px[LY_WGRAD_GROUP_MAX];
-  float* slab[LY_WGRAD_GROUP_MAX];       // per problem: [chunks][tiles][BN * BK] partial tiles (the slab form), else unused
-  int tiles_k[LY_WGRAD_GROUP_MAX], tiles[LY_WGRAD_GROUP_MAX], blk0[LY_WGRAD_GROUP_MAX + 1];
-  int chunks[LY_WGRAD_GROUP_MAX], cblk0[LY_WGRAD_GROUP_MAX + 1];      // combine launch: chunks per problem, first combine block per problem
-  int n;
-};
+// often per pixel, and the launch fills the chip where a lone small problem leaves a ragged second wave.  (LyWgradGroupArgs: ly_wgrad.hpp)
 template <typename T, int BN, int BK, int P, bool ROWS, bool PRO = false, bool GSLAB = false, bool OCT = false>
 __global__ __launch_bounds__(LY_THREADS) __attribute__((amdgpu_waves_per_eu(BN + BK > 160 ? 2 : 3))) void ly_wgrad_tiled_group_kernel(const LyWgradGroupArgs G) {
   const int bid = ly_xcd_remap((int)blockIdx.x, (int)gridDim.x);            // (see ly_wgrad_tiled_kernel)
@@ -988,6 +979,13 @@ static bool wgrad_octets(const LyWgradParams& Q) {
   return (Q.N & 7) == 0 && (Q.Cin & 7) == 0 && (Q.lddu & 7) == 0 && (Q.ldx & 7) == 0 && ((uintptr_t)Q.du & 15) == 0 && ((uintptr_t)Q.x & 15) == 0;
 }
 
+static int g_ly_wgrad1 = 1;
+extern "C" int ly_tune_wgrad1(int on) {                            // development switch: 0 sends plain-row 1x1 bf16 problems back to ly_wgrad_tiled_body
+  const int was = g_ly_wgrad1;
+  g_ly_wgrad1 = on;
+  return was;
+}
+
 template <typename T, int BN, int BK, int P>
 static int launch_wgrad_tiled(const LyWgradParams& Q, bool rows, hipStream_t st) {
   const int Ktot = Q.ks * Q.ks * Q.Cin;
@@ -1014,6 +1012,9 @@ static int launch_wgrad_tiled(const LyWgradParams& Q, bool rows, hipStream_t st)
   const bool pro = rows && Q.x_scale;
   const auto launch = [&]() -> int {
     if constexpr (LyT<T>::BF) {
+      // plain rows in whole 16-byte vectors, no prologue: [pixel][channel] LDS tiles and transposed fragment reads (ly_wgrad1.hip), same grid,
+      // chunks and slab; several chunks without a slab keep the atomic flush of the kernel below
+      if (g_ly_wgrad1 && rows && !pro && wgrad_octets<T>(Q) && (slab || chunks == 1)) return ly_wgrad1_launch(Q, BN, BK, grid, tiles_k, chunk_px, slab, st);
       if (wgrad_octets<T>(Q)) return !rows ? WG_TILED(false, false, true) : pro ? WG_TILED(true, true, true) : WG_TILED(true, false, true);
     }
     return !rows ? WG_TILED(false, false, false) : pro ? WG_TILED(true, true, false) : WG_TILED(true, false, false);
@@ -1096,6 +1097,7 @@ static int wgrad_group_launch(const LyWgradParams* arr, int n, hipStream_t st) {
   const auto launch = [&]() -> int {
     if (!gslab) return any_pro ? WG_GROUP(true, false, false) : WG_GROUP(false, false, false);
     if constexpr (LyT<T>::BF) {
+      if (g_ly_wgrad1 && oct && !any_pro) return ly_wgrad1_group_launch(G, st);      // every member eligible: the grouped form of ly_wgrad1.hip
       if (oct) return any_pro ? WG_GROUP(true, true, true) : WG_GROUP(false, true, true);
     }
     return any_pro ? WG_GROUP(true, true, false) : WG_GROUP(false, true, false);

@@ -1,11 +1,27 @@
-// What the weight-gradient translation units share: ly_backward.hip (the generic tiled kernels and the dispatch) and ly_wgrad3.hip (3x3 /
-// stride 1 / pad 1, bf16).
+// What the weight-gradient translation units share: ly_backward.hip (the generic tiled kernels and the dispatch), ly_wgrad3.hip (3x3 /
+// stride 1 / pad 1, bf16) and ly_wgrad1.hip (plain-row 1x1, bf16, 16-byte friendly widths).
 #pragma once
 #include "ly_common.hpp"
 #include "ly_params.h"
 
 bool ly_wgrad3_ok(const LyWgradParams& P);                         // ly_wgrad3.hip
 int ly_wgrad3_launch(const LyWgradParams& P, hipStream_t st);
+
+// Several independent weight gradients of ONE tile class in one launch (ly_wgrad_group): what the grouped kernels and their fold take
+#define LY_WGRAD_GROUP_MAX 4
+struct LyWgradGroupArgs {
+  LyWgradParams p[LY_WGRAD_GROUP_MAX];
+  long chunk_px[LY_WGRAD_GROUP_MAX];
+  float* slab[LY_WGRAD_GROUP_MAX];       // per problem: [chunks][tiles][BN * BK] partial tiles (the slab form), else unused
+  int tiles_k[LY_WGRAD_GROUP_MAX], tiles[LY_WGRAD_GROUP_MAX], blk0[LY_WGRAD_GROUP_MAX + 1];
+  int chunks[LY_WGRAD_GROUP_MAX], cblk0[LY_WGRAD_GROUP_MAX + 1];      // combine launch: chunks per problem, first combine block per problem
+  int n;
+};
+
+// ly_wgrad1.hip: the launches of launch_wgrad_tiled / wgrad_group_launch (ly_backward.hip) for a problem the caller found eligible — same grid,
+// chunking and slab; slab == nullptr (one chunk only) adds to dw directly
+int ly_wgrad1_launch(const LyWgradParams& P, int BN, int BK, dim3 grid, int tiles_k, long chunk_px, float* slab, hipStream_t st);
+int ly_wgrad1_group_launch(const LyWgradGroupArgs& G, hipStream_t st);
 
 // The fold of a slab launch's partial tiles: *d += sum over chunks of p[chunk * E], in a fixed order whatever the block count of the producing
 // launch, one writer per element.  Block = 64 slab columns (threadIdx & 63) x rls row lanes (threadIdx >> 6) that walk the chunks: 16 for

@@ -1241,7 +1241,7 @@ def wgrad(*, M, H, W, N, du, lddu, x, ldx, Hin, Win, Cin, dw, lddw, ks=1, stride
     P = _wgrad_params(**q)
     with _Timed(wgrad_kernel_name(_tname(x), N, ks * ks * Cin, ks == 1 and stride == 1 and pad == 0 and not nchw and not up2,
                                   (not nchw) and N % 4 == 0 and Cin % 4 == 0 and lddu % 4 == 0 and ldx % 4 == 0, x_scale is not None,
-                                  _wgrad_octets(x, du, N, Cin, lddu, ldx, du_off, x_off)),
+                                  _wgrad_octets(x, du, N, Cin, lddu, ldx, du_off, x_off), m=M, ws_floats=P.ws_floats if P.ws else 0),
                 2.0 * M * N * ks * ks * Cin, x.element_size() * M * (N + Cin) + 4.0 * N * ks * ks * Cin):
         capi.check(capi.lib().ly_wgrad(ctypes.byref(P), capi.stream_ptr()), "ly_wgrad")
 
@@ -1380,8 +1380,11 @@ def wgrad_group(problems, _now=False):
     anyp = any(q.get("x_scale") is not None for q in problems)
     gslab = wgrad_workspace(x0.device) is not None                               # slab flush + ly_wgrad_combine_group_kernel (wgrad_group_launch)
     octs = gslab and all(_wgrad_octets(q["x"], q["du"], q["N"], q["Cin"], q["lddu"], q["ldx"], q.get("du_off", 0), q.get("x_off", 0)) for q in problems)
-    with _Timed(f"ly_wgrad_tiled_group_kernel<{_tname(x0)}, 128, 128, {px}, true, {'true' if anyp else 'false'}, {'true' if gslab else 'false'}, "
-                f"{'true' if octs else 'false'}>", sum(2.0 * q["M"] * q["N"] * q["Cin"] for q in problems),
+    name = (f"ly_wgrad_tiled_group_kernel<{_tname(x0)}, 128, 128, {px}, true, {'true' if anyp else 'false'}, {'true' if gslab else 'false'}, "
+            f"{'true' if octs else 'false'}>")
+    if WGRAD1 and octs and not anyp:                                             # (octs implies the slab form: wgrad_group_launch)
+        name = "ly_wgrad1_group_kernel"
+    with _Timed(name, sum(2.0 * q["M"] * q["N"] * q["Cin"] for q in problems),
                 sum(x0.element_size() * q["M"] * (q["N"] + q["Cin"]) + 4.0 * q["N"] * q["Cin"] for q in problems)):
         capi.check(capi.lib().ly_wgrad_group(arr, len(problems), capi.stream_ptr()), "ly_wgrad_group")
 
@@ -1393,8 +1396,20 @@ def _wgrad_octets(x, du, n, cin, lddu, ldx, du_off=0, x_off=0):
             and (du.data_ptr() + 2 * du_off) % 16 == 0 and (x.data_ptr() + 2 * x_off) % 16 == 0)
 
 
-def wgrad_kernel_name(t, n, ktot, rows, tiled, pro=False, octets=False):
-    """mirror of the tile dispatch in csrc/ly_backward.hip (wgrad_dispatch): the kernel name rocprofv3 prints"""
+WGRAD1 = True                       # mirror of ly_tune_wgrad1 (csrc/ly_backward.hip); change both through tune_wgrad1
+
+
+def tune_wgrad1(on):
+    """0 sends the plain-row 1x1 bf16 weight gradients back to the register-transposing tiled kernel (A/B timing, the equivalence tests);
+    returns the previous setting"""
+    global WGRAD1
+    WGRAD1 = bool(on)
+    return capi.lib().ly_tune_wgrad1(int(bool(on)))
+
+
+def wgrad_kernel_name(t, n, ktot, rows, tiled, pro=False, octets=False, m=None, ws_floats=0):
+    """mirror of the tile dispatch in csrc/ly_backward.hip (wgrad_dispatch, launch_wgrad_tiled): the kernel name rocprofv3 prints.  m / ws_floats
+    (pixels, floats of scratch) decide between the slab and the atomic flush, which the kernel of csrc/ly_wgrad1.hip is dispatched on."""
     r = "true" if rows else "false"
     if not tiled:
         return f"ly_wgrad_kernel<{t}, {r}>"
@@ -1407,6 +1422,14 @@ def wgrad_kernel_name(t, n, ktot, rows, tiled, pro=False, octets=False):
         bn, bk = 64, 128
     else:
         bn, bk = 128, 128
+    if WGRAD1 and rows and octets and not pro and m is not None:
+        tiles = -(-n // bn) * -(-ktot // bk)
+        chunks = max(1, min(-(-512 // tiles), -(-m // 512)))
+        chunk_px = -(-(-(-m // chunks)) // px) * px
+        chunks = -(-m // chunk_px)
+        slab = chunks > 1 and chunks * tiles * bn * bk <= ws_floats
+        if slab or chunks == 1:
+            return f"ly_wgrad1_kernel<{bn}, {bk}, {'true' if slab else 'false'}>"
     return f"ly_wgrad_tiled_kernel<{t}, {bn}, {bk}, {px}, {r}, {'true' if pro and rows else 'false'}, {'true' if octets else 'false'}>"
 
 
