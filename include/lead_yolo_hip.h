@@ -559,11 +559,19 @@ int ly_wgrad(const LyWgradParams* p, void* stream);
  * gather) and n <= 4: they share the launch's ~512 blocks, so every block walks a longer pixel chunk (fewer first-load waits and atomic tile
  * flushes per pixel).  Any other mix: the same as n calls of ly_wgrad.                                                                  */
 int ly_wgrad_group(const LyWgradParams* arr, int n, void* stream);
-/* development switch (returns the previous value): 0 sends 3x3 / stride-1 bf16 problems to the generic tiled kernel instead of the halo-tile
- * kernel of csrc/ly_wgrad3.hip (A/B timing and the equivalence test); default 1.                                                           */
+/* What ly_wgrad(arr) (n == 1) or ly_wgrad_group(arr, n) (n >= 2) would launch: the name of the contraction kernel as rocprofv3 prints it,
+ * e.g. "ly_wgrad1_kernel<32, 128, true>", written to name, NUL-terminated, in at most cap bytes (a longer name is cut).  It is formatted
+ * from the launch plan the call itself would run (csrc/ly_wgrad.hip), fold launches not counted.  Host only: nothing is launched and no
+ * device is touched; du / x / dw / ws are not dereferenced — their addresses enter the alignment tests, ws and ws_floats the choice of the
+ * flush.  Returns 0; 1 when n >= 2 and the group would not be ONE launch but n calls of ly_wgrad (name: the kernel of the last of them);
+ * <0 with ly_last_error() for bad arguments or a problem ly_wgrad refuses.                                                               */
+int ly_wgrad_describe(const LyWgradParams* arr, int n, char* name, int cap);
+/* development switch (returns the previous value): 0 sends 3x3 / stride-1 bf16 problems to the generic tiled kernel of csrc/ly_wgrad.hip
+ * instead of the halo-tile kernel of csrc/ly_wgrad3.hip (A/B timing and the equivalence test); default 1.                                  */
 int ly_tune_wgrad3(int on);
 /* development switch (returns the previous value): 0 sends plain-row 1x1 bf16 problems with 16-byte friendly widths to the register-transposing
- * tiled kernel instead of the transposed-read kernel of csrc/ly_wgrad1.hip (A/B timing and the equivalence test); default 1.               */
+ * tiled kernel of csrc/ly_wgrad.hip instead of the transposed-read kernel of csrc/ly_wgrad1.hip (A/B timing and the equivalence test);
+ * default 1.                                                                                                                                */
 int ly_tune_wgrad1(int on);
 
 /* Adjoint of the nearest-2x read: out[n,h,w,:] = sum of d[n, 2h+{0,1}, 2w+{0,1}, :]  (d is a 2Hs x 2Ws map).      */

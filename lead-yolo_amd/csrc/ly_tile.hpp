@@ -134,6 +134,14 @@ __device__ __forceinline__ bf16x8 ly_cat8(const bf16x4 a, const bf16x4 b) {
   return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
+__device__ __forceinline__ void ly_split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
+  bf16x4 h0, l0, h1, l1;
+  ly_split4((f32x4){v[0], v[1], v[2], v[3]}, h0, l0);
+  ly_split4((f32x4){v[4], v[5], v[6], v[7]}, h1, l1);
+  hi = ly_cat8(h0, h1);
+  lo = ly_cat8(l0, l1);
+}
+
 __device__ __forceinline__ f32x4 ly_mfma_bf16(const bf16x8 a, const bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }

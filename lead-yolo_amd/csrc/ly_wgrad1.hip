@@ -1,6 +1,6 @@
 // Weight gradient of a plain-row 1x1 convolution, bf16 storage, gfx950:
 //      dW[n][c] += sum over pixels p of  du[p][n] * x[p][c]
-// for the problems the octet staging of ly_wgrad_tiled_body (ly_backward.hip) took: N, Cin, lddu, ldx multiples of 8, 16-byte aligned bases,
+// for the problems the octet staging of ly_wgrad_tiled_body (ly_wgrad.hip) took: N, Cin, lddu, ldx multiples of 8, 16-byte aligned bases,
 // no gather, no x prologue.  That kernel transposes both operands in registers on their way into [channel][pixel] LDS planes (32 v_perm_b32
 // per 8 x 8 piece, a zero select per load, 64 staging registers: the vector pipe was busy half the time in a kernel that should stream).  Here,
 // as in ly_wgrad3.hip,
@@ -12,7 +12,7 @@
 //   * rows past the chunk's end and channel pieces past N / Cin are loaded from a valid address and written to LDS as zeros: the loop body is
 //     straight-line, no load under a branch, EXEC all ones at every transposed read.
 // Block tile, wave split (2 x 2), accumulator layout, chunking and the slab format [chunk][tile][BN * BK] are those of ly_wgrad_tiled_body: the
-// fold kernels of ly_backward.hip are reused as they are, and the fold order is unchanged.
+// fold kernels of ly_wgrad.hip are reused as they are, and the fold order is unchanged.
 // LDS image of a step: du tile [64 px][2 BN + 32 B] | x tile [64 px][2 BK + 32 B].  The row strides are 32 x odd bytes: the 8 pixel rows x 32
 // bytes a half-wave's transposed read touches hit all 64 banks once, and a staging store is 16 bytes x consecutive lanes of one row.
 #include "ly_tile.hpp"
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(LY_THREADS) __attribute__((amdgpu_waves_per_eu(W1<B
   ly_wgrad1_body<BN, BK, SLAB>(P, (int)blockIdx.x, (int)blockIdx.y, tiles_k, chunk_px, slab, (int)gridDim.x);
 }
 
-// the grouped launch of ly_wgrad_tiled_group_kernel (ly_backward.hip: same arguments, same block-to-problem map), slab form
+// the grouped launch of ly_wgrad_tiled_group_kernel (ly_wgrad.hip: same arguments, same block-to-problem map), slab form
 __global__ __launch_bounds__(LY_THREADS) __attribute__((amdgpu_waves_per_eu(W1<128, 128>::WAVES))) void ly_wgrad1_group_kernel(const LyWgradGroupArgs G) {
   const int bid = ly_xcd_remap((int)blockIdx.x, (int)gridDim.x);
   int g = 0;
@@ -211,24 +211,28 @@ __global__ __launch_bounds__(LY_THREADS) __attribute__((amdgpu_waves_per_eu(W1<1
 }
 
 template <int BN, int BK>
-static int wgrad1_launch_tile(const LyWgradParams& Q, const dim3 grid, const int tiles_k, const long chunk_px, float* const slab, hipStream_t st) {
-  if (slab) return ly_launch_lds<ly_wgrad1_kernel<BN, BK, true>>(grid, dim3(LY_THREADS), (size_t)W1<BN, BK>::LDS, st, Q, tiles_k, chunk_px, slab);
-  return ly_launch_lds<ly_wgrad1_kernel<BN, BK, false>>(grid, dim3(LY_THREADS), (size_t)W1<BN, BK>::LDS, st, Q, tiles_k, chunk_px, slab);
+static int wgrad1_launch_tile(const LyWgradParams& Q, const dim3 grid, const int tiles_k, const long chunk_px, float* const slab, const LyWgOut& out) {
+#define W1_LAUNCH(SLAB_)                                                                                                                          \
+  LY_WG_EMIT(out, (ly_launch_lds<ly_wgrad1_kernel<BN, BK, SLAB_>>(grid, dim3(LY_THREADS), (size_t)W1<BN, BK>::LDS, out.st, Q, tiles_k, chunk_px, slab)), \
+             "ly_wgrad1_kernel<%d, %d, " #SLAB_ ">", BN, BK)
+  return slab ? W1_LAUNCH(true) : W1_LAUNCH(false);
+#undef W1_LAUNCH
 }
 
 int ly_wgrad1_launch(const LyWgradParams& Q, const int BN, const int BK, const dim3 grid, const int tiles_k, const long chunk_px, float* const slab,
-                     hipStream_t st) {
+                     const LyWgOut& out) {
   LY_CHECK(chunk_px % W1_PX == 0, "wgrad1: chunk of %ld pixels is not a whole number of steps", chunk_px);
   LY_CHECK(slab || grid.y == 1, "wgrad1: several chunks need the slab");
-  if (BN == 128 && BK == 128) return wgrad1_launch_tile<128, 128>(Q, grid, tiles_k, chunk_px, slab, st);
-  if (BN == 64 && BK == 128) return wgrad1_launch_tile<64, 128>(Q, grid, tiles_k, chunk_px, slab, st);
-  if (BN == 32 && BK == 128) return wgrad1_launch_tile<32, 128>(Q, grid, tiles_k, chunk_px, slab, st);
-  if (BN == 64 && BK == 64) return wgrad1_launch_tile<64, 64>(Q, grid, tiles_k, chunk_px, slab, st);
+  if (BN == 128 && BK == 128) return wgrad1_launch_tile<128, 128>(Q, grid, tiles_k, chunk_px, slab, out);
+  if (BN == 64 && BK == 128) return wgrad1_launch_tile<64, 128>(Q, grid, tiles_k, chunk_px, slab, out);
+  if (BN == 32 && BK == 128) return wgrad1_launch_tile<32, 128>(Q, grid, tiles_k, chunk_px, slab, out);
+  if (BN == 64 && BK == 64) return wgrad1_launch_tile<64, 64>(Q, grid, tiles_k, chunk_px, slab, out);
   LY_CHECK(false, "wgrad1: no %d x %d tile", BN, BK);
   return 0;
 }
 
-int ly_wgrad1_group_launch(const LyWgradGroupArgs& G, hipStream_t st) {
+int ly_wgrad1_group_launch(const LyWgradGroupArgs& G, const LyWgOut& out) {
   for (int g = 0; g < G.n; ++g) LY_CHECK(G.chunk_px[g] % W1_PX == 0 && G.slab[g], "wgrad1: group member %d has no slab or a ragged chunk", g);
-  return ly_launch_lds<ly_wgrad1_group_kernel>(dim3((unsigned)G.blk0[G.n]), dim3(LY_THREADS), (size_t)W1<128, 128>::LDS, st, G);
+  return LY_WG_EMIT(out, (ly_launch_lds<ly_wgrad1_group_kernel>(dim3((unsigned)G.blk0[G.n]), dim3(LY_THREADS), (size_t)W1<128, 128>::LDS, out.st, G)),
+                    "ly_wgrad1_group_kernel");
 }

@@ -2,7 +2,7 @@
 // models/common.py:1890-1910, and of Partial_conv3.partial_conv3, models/common.py:1412-1437):
 //      dW[o][tap][c] += sum over pixels p of  du[p][o] * x[p + tap][c]
 //
-// The generic tiled kernel (ly_backward.hip) treats the nine taps as nine separate K tiles: every tap re-gathers x through L2 and re-reads
+// The generic tiled kernel (ly_wgrad.hip) treats the nine taps as nine separate K tiles: every tap re-gathers x through L2 and re-reads
 // the whole du slab (PMC: 3.7-4.9x the algorithmic HBM bytes, MFMA pipe 7-10 % busy), and it transposes both operands in registers on
 // their way into [channel][pixel] LDS planes, a layout in which a tap shift is an unaligned access.  Here
 //   * both operands stay in their global layout, [pixel][channel], in LDS: staging is a plain 16-byte copy, and the MFMA fragments (the

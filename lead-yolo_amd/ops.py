@@ -1239,11 +1239,18 @@ def wgrad(*, M, H, W, N, du, lddu, x, ldx, Hin, Win, Cin, dw, lddw, ks=1, stride
     if not _now and _wgrad_deferrable(q):
         return _wgrad_enqueue(q)
     P = _wgrad_params(**q)
-    with _Timed(wgrad_kernel_name(_tname(x), N, ks * ks * Cin, ks == 1 and stride == 1 and pad == 0 and not nchw and not up2,
-                                  (not nchw) and N % 4 == 0 and Cin % 4 == 0 and lddu % 4 == 0 and ldx % 4 == 0, x_scale is not None,
-                                  _wgrad_octets(x, du, N, Cin, lddu, ldx, du_off, x_off), m=M, ws_floats=P.ws_floats if P.ws else 0),
-                2.0 * M * N * ks * ks * Cin, x.element_size() * M * (N + Cin) + 4.0 * N * ks * ks * Cin):
+    with _Timed(_wgrad_label(ctypes.byref(P), 1), 2.0 * M * N * ks * ks * Cin, x.element_size() * M * (N + Cin) + 4.0 * N * ks * ks * Cin):
         capi.check(capi.lib().ly_wgrad(ctypes.byref(P), capi.stream_ptr()), "ly_wgrad")
+
+
+def _wgrad_label(arr, n):
+    """the `_Timed` name of ly_wgrad (n = 1) / ly_wgrad_group on these LyWgradParams: the kernel the library says it would launch, as
+    rocprofv3 prints it (ly_wgrad_describe).  Asked only while a profile is recorded; a refused problem is reported by the launch itself."""
+    if PROFILE is None:
+        return None
+    name = ctypes.create_string_buffer(128)
+    rc = capi.lib().ly_wgrad_describe(arr, n, name, len(name))
+    return name.value.decode() if rc >= 0 else "ly_wgrad"
 
 
 def _wgrad_params(*, M, H, W, N, du, lddu, x, ldx, Hin, Win, Cin, dw, lddw, ks=1, stride=1, pad=0, nchw=False, up2=False, du_off=0, x_off=0,
@@ -1376,61 +1383,15 @@ def wgrad_group(problems, _now=False):
         return
     arr = (capi.LyWgradParams * len(problems))(*[_wgrad_params(**q) for q in problems])
     x0 = problems[0]["x"]
-    px = 128 if x0.dtype == torch.bfloat16 else 64
-    anyp = any(q.get("x_scale") is not None for q in problems)
-    gslab = wgrad_workspace(x0.device) is not None                               # slab flush + ly_wgrad_combine_group_kernel (wgrad_group_launch)
-    octs = gslab and all(_wgrad_octets(q["x"], q["du"], q["N"], q["Cin"], q["lddu"], q["ldx"], q.get("du_off", 0), q.get("x_off", 0)) for q in problems)
-    name = (f"ly_wgrad_tiled_group_kernel<{_tname(x0)}, 128, 128, {px}, true, {'true' if anyp else 'false'}, {'true' if gslab else 'false'}, "
-            f"{'true' if octs else 'false'}>")
-    if WGRAD1 and octs and not anyp:                                             # (octs implies the slab form: wgrad_group_launch)
-        name = "ly_wgrad1_group_kernel"
-    with _Timed(name, sum(2.0 * q["M"] * q["N"] * q["Cin"] for q in problems),
+    with _Timed(_wgrad_label(arr, len(problems)), sum(2.0 * q["M"] * q["N"] * q["Cin"] for q in problems),
                 sum(x0.element_size() * q["M"] * (q["N"] + q["Cin"]) + 4.0 * q["N"] * q["Cin"] for q in problems)):
         capi.check(capi.lib().ly_wgrad_group(arr, len(problems), capi.stream_ptr()), "ly_wgrad_group")
-
-
-def _wgrad_octets(x, du, n, cin, lddu, ldx, du_off=0, x_off=0):
-    """mirror of wgrad_octets (csrc/ly_backward.hip): the 16-byte staging form applies — bf16 storage, widths / strides / addresses in whole
-    8-channel vectors"""
-    return (x.dtype == torch.bfloat16 and n % 8 == 0 and cin % 8 == 0 and lddu % 8 == 0 and ldx % 8 == 0
-            and (du.data_ptr() + 2 * du_off) % 16 == 0 and (x.data_ptr() + 2 * x_off) % 16 == 0)
-
-
-WGRAD1 = True                       # mirror of ly_tune_wgrad1 (csrc/ly_backward.hip); change both through tune_wgrad1
 
 
 def tune_wgrad1(on):
     """0 sends the plain-row 1x1 bf16 weight gradients back to the register-transposing tiled kernel (A/B timing, the equivalence tests);
     returns the previous setting"""
-    global WGRAD1
-    WGRAD1 = bool(on)
     return capi.lib().ly_tune_wgrad1(int(bool(on)))
-
-
-def wgrad_kernel_name(t, n, ktot, rows, tiled, pro=False, octets=False, m=None, ws_floats=0):
-    """mirror of the tile dispatch in csrc/ly_backward.hip (wgrad_dispatch, launch_wgrad_tiled): the kernel name rocprofv3 prints.  m / ws_floats
-    (pixels, floats of scratch) decide between the slab and the atomic flush, which the kernel of csrc/ly_wgrad1.hip is dispatched on."""
-    r = "true" if rows else "false"
-    if not tiled:
-        return f"ly_wgrad_kernel<{t}, {r}>"
-    px = 128 if t == "__bf16" else 64             # one 272-byte LDS row per channel and step in both dtypes, single buffer
-    if n <= 64 and ktot <= 64:
-        bn, bk = 64, 64
-    elif n <= 32:
-        bn, bk = 32, 128
-    elif n <= 64:
-        bn, bk = 64, 128
-    else:
-        bn, bk = 128, 128
-    if WGRAD1 and rows and octets and not pro and m is not None:
-        tiles = -(-n // bn) * -(-ktot // bk)
-        chunks = max(1, min(-(-512 // tiles), -(-m // 512)))
-        chunk_px = -(-(-(-m // chunks)) // px) * px
-        chunks = -(-m // chunk_px)
-        slab = chunks > 1 and chunks * tiles * bn * bk <= ws_floats
-        if slab or chunks == 1:
-            return f"ly_wgrad1_kernel<{bn}, {bk}, {'true' if slab else 'false'}>"
-    return f"ly_wgrad_tiled_kernel<{t}, {bn}, {bk}, {px}, {r}, {'true' if pro and rows else 'false'}, {'true' if octets else 'false'}>"
 
 
 def sum_rows(t, out=None, accumulate=False):

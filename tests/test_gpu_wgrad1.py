@@ -146,6 +146,26 @@ def test_wgrad1_tile_classes_and_ragged_pixel_runs(shape):
 
 
 @pytest.mark.gpu
+def test_wgrad_profile_records_carry_the_described_kernel(monkeypatch):
+    """with ops.PROFILE recording, ops.wgrad labels its record with what ly_wgrad_describe says for the parameters it launches (the offsets
+    folded into the pointers), for an eligible and an ineligible shape; the results are the unprofiled ones' judge"""
+    import ctypes
+    import lead_yolo_amd as L
+    monkeypatch.setattr(L.ops, "PROFILE", [])
+    want = []
+    for (n, c), name in [(SHAPES[0], "ly_wgrad1_kernel<32, 128, true>"), (SHAPES[-1], "ly_wgrad_tiled_kernel<__bf16, 64, 64, 128, true, false, false>")]:
+        case = _Case(1440, n, c, seed=5, **({} if n % 8 == 0 else dict(du_off=4, du_pad=4, x_off=4, x_pad=4)))
+        dw = case.fresh()
+        L.ops.wgrad(dw=dw, _now=True, **case.q)
+        case.check(dw, f"profiled M=1440 N={n} Cin={c}")
+        buf = ctypes.create_string_buffer(128)
+        assert L.capi.lib().ly_wgrad_describe(ctypes.byref(L.ops._wgrad_params(dw=dw, **case.q)), 1, buf, len(buf)) == 0
+        assert buf.value.decode() == name
+        want.append(name)
+    assert [rec[0] for rec in L.ops.PROFILE] == want
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("kw", [dict(du_off=16, du_pad=40, x_off=0, x_pad=0), dict(du_off=0, du_pad=0, x_off=24, x_pad=16),
                                 dict(dw_off=40, dw_pad=0), dict(dw_off=8, dw_pad=24, n_valid=18), dict(c_valid=100), dict(n_valid=18, c_valid=3)],
                          ids=["du-slice", "x-slice", "concat-second-source", "n_valid", "c_valid", "both-valid"])
