@@ -463,6 +463,44 @@ int ly_val_advance(int* cursor, int bs, void* stream);
 int ly_val_confusion(const float* dets, const int* counts, int bs, int max_det, const float* targets, long nt, int W, int H,
                      const float* shapes, float conf_thres, float iou_thres, int single_cls, int nc, int* matrix, int* flags, void* stream);
 
+/* ---- autoanchor on the device (csrc/ly_anchors.hip; utils/autoanchor.py check_anchors / kmean_anchors) -----------------------------------
+ * No atomics: every kernel leaves per-block partials in a caller-allocated slab of `slices` rows, folded in index order.  na (anchors in
+ * a set, all levels together) <= LY_ANCHOR_NA_MAX, 1 <= slices <= LY_ANCHOR_SLICES_MAX; slice s covers labels [s * ceil(n / slices), ...).
+ * thr is hyp['anchor_t']; the kernels compare with float32(1 / thr), as torch does for a float32 tensor and a Python scalar.              */
+#define LY_ANCHOR_NA_MAX 16
+#define LY_ANCHOR_SLICES_MAX 1024
+/* autoanchor.py:34-36 (check_anchors) and :128-129 (kmean_anchors), `l[:, 3:5] * s`: wh[j] = float32(labels[j, 3:5] * (shapes[img[j]] *
+ * scale[img[j]])), the products in float64.  labels [n, 5] (class, xywh normalised), img [n] the label's image, shapes [n_img, 2] = (w, h)
+ * already normalised to img_size * shape / shape.max(), scale NULL or [n_img].  An image index outside [0, n_img) gives NaN.              */
+int ly_anchor_wh(const double* labels, const int* img, long n, const double* shapes, int n_img, const double* scale, float* wh, void* stream);
+/* autoanchor.py:38-44 (`metric` of check_anchors: bpr, aat) and :104-112 (`metric` / `anchor_fitness` of kmean_anchors) for G candidate
+ * sets k [G, na, 2] at once, grid slices x G:  r = wh / k, x = min over the two sides of min(r, 1 / r), best = max over anchors of x;
+ * part [slices][G][3] doubles = (sum of best * (best > 1/thr), count of best > 1/thr, count of x > 1/thr) per slice, the counts exact
+ * integers.  ly_sum_rows_f64(part, slices, 3 * G, out) folds them.                                                                       */
+int ly_anchor_metric(const float* wh, long n, const float* k, int G, int na, double thr, int slices, double* part, void* stream);
+/* autoanchor.py:156-165, the `for _ in pbar` loop of kmean_anchors, B generations per pair of launches.  v [gen, na, 2] doubles: the
+ * mutation factors of every generation (they do not depend on k; drawn by the host).  k [na, 2] doubles, f [1] double (the fitness SUM over
+ * the labels, not the mean), cursor [2] ints = (generation, acceptances) live in device memory.
+ * eval: candidate c < B is kg = float32(max(k * v[cursor[0] + c], 2.0)); part [slices][B] = its fitness sum per slice (0 past gen).
+ * pick (one block): folds the slices in index order; the lowest c with fg_c > f is accepted: k = max(k * v[g + c], 2.0) in double,
+ * f = fg_c, cursor[0] += c + 1, cursor[1] += 1; none: cursor[0] += B.  cursor[0] stops at gen.  B <= 256.                                 */
+int ly_anchor_evolve_eval(const float* wh, long n, const double* v, int gen, int na, const double* k, const int* cursor, int B, double thr,
+                          int slices, double* part, void* stream);
+int ly_anchor_evolve_pick(const double* part, int slices, int B, const double* v, int gen, int na, double* k, double* f, int* cursor,
+                          void* stream);
+/* autoanchor.py:140 `kmeans(wh / s, n, iter=30)` (scipy.cluster.vq: _kmeans, vq, update_cluster_means): one Lloyd iteration of R
+ * independent runs over the same whitened points pts [n, 2], centroids cent [R, na, 2] float32.
+ * assign, grid slices x R: nearest centroid by dx*dx + dy*dy in float32 (lowest index on equality); part [slices][R][3 na + 1] doubles =
+ * (sum x, sum y, count) per centroid, then the sum of sqrtf(d2).  assign: NULL or [R, n] ints, the chosen centroid.  Runs with
+ * flags[r] != 0 are skipped by both kernels.
+ * update (one block): centroid = float32(sum / count) in double, dist[r] = the mean distance (set dist to +inf before the first
+ * iteration), count [R, na], iters[r] += 1; flags[r] bit 0: closed, |previous dist - dist| <= thresh; bit 1 (with bit 0): discarded, a
+ * centroid lost all its points — the run keeps its centroids.  active[0] = runs still open.  R <= 256.                                   */
+int ly_kmeans_assign(const float* pts, long n, const float* cent, int R, int na, const int* flags, int slices, double* part, int* assign,
+                     void* stream);
+int ly_kmeans_update(const double* part, int slices, int R, int na, long n, double thresh, float* cent, double* dist, int* count, int* flags,
+                     int* iters, int* active, void* stream);
+
 /* ---- detect input path on the device (csrc/ly_letterbox.hip; detect.py, utils/dataloaders.py LoadImages.__next__ / load_image) -----------
  * A LyLetterboxImage describes one output canvas: the source picture (as cv2.imread or a decoder hands it over) resized to nh x nw, placed
  * with its corner at (top, left), 114 everywhere else.  The host computes nh, nw, top, left with letterbox's own arithmetic

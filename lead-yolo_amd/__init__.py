@@ -16,3 +16,4 @@ from .mosaic import ImageBank, MosaicAugment  # noqa: F401,E402
 from .metrics import ConfusionMatrix, MatchAccumulator, Validator, ValResult, ap_per_class, compute_ap, match_padded, unpack_correct  # noqa: F401,E402
 from .predict import Detector, LetterboxPlan, letterbox, letterbox_plan, load_image_size, scale_boxes  # noqa: F401,E402
 from .valrun import ValPlan, ValRun, ValSet, val_labels, val_plan, validate  # noqa: F401,E402
+from .anchors import AnchorCheck, anchor_metric, check_anchors, evolve, kmean_anchors, kmeans, label_wh, mutation_table  # noqa: F401,E402

@@ -95,6 +95,7 @@ def _parse_header(path):
 _DEFINES, _STRUCTS, SIGNATURES, RESTYPES = _parse_header(HEADER_PATH)
 globals().update(_STRUCTS)
 STATS_STRIPES, F64_ADD_MAX, SCALE_IMG_MAX = _DEFINES["LY_STATS_STRIPES"], _DEFINES["LY_F64_ADD_MAX"], _DEFINES["LY_SCALE_IMG_MAX"]
+ANCHOR_NA_MAX, ANCHOR_SLICES_MAX = _DEFINES["LY_ANCHOR_NA_MAX"], _DEFINES["LY_ANCHOR_SLICES_MAX"]
 
 # the semantic constants keep their Python spelling (tests/test_capi_abi.py holds them to the header's enums)
 LY_F32, LY_BF16 = 0, 1                     # `dtype` codes of the C ABI

@@ -47,10 +47,11 @@ class ComputeLoss:
 
     def _consts(self, device, cells):
         k = self._const.get(device)
-        if k is None or k["cells_key"] != tuple(cells):
+        key = (tuple(cells), self.anchors._version)      # the float32 anchors may be a COPY of the buffer (bf16 model, other device): an
+        if k is None or k["cells_key"] != key:            # in-place write to it (anchors.check_anchors) bumps its version
             k = dict(cells=torch.tensor([float(c) for c in cells], device=device),
                      balance=torch.tensor([float(b) for b in self.balance[:len(cells)]], device=device),
-                     anchors=[self.anchors[i].to(device).float().contiguous() for i in range(self.nl)], cells_key=tuple(cells))
+                     anchors=[self.anchors[i].to(device).float().contiguous() for i in range(self.nl)], cells_key=key)
             self._const[device] = k
         return k
 

@@ -1484,3 +1484,60 @@ def maxpool_bwd(x, x_off, ldx, dy, dy_off, lddy, n, h, w, c, k, dx, dx_off, lddx
     assert dy.dtype == torch.float32 and dx.dtype == torch.float32
     capi.check(capi.lib().ly_maxpool_bwd(at(x, x_off), ldx, at(dy, dy_off), lddy, n, h, w, c, k, at(dx, dx_off), lddx, capi.dtype_code(x),
                                          capi.stream_ptr()), "ly_maxpool_bwd")
+
+
+# ---- autoanchor (csrc/ly_anchors.hip; lead-yolo_amd/anchors.py holds the host loops) ------------------------------------------------
+ANCHOR_NA_MAX, ANCHOR_SLICES_MAX = capi.ANCHOR_NA_MAX, capi.ANCHOR_SLICES_MAX
+
+
+def anchor_slices(n, slices=None):
+    """label slices of a launch: one per 1024 labels, at most 64, unless the caller names a count"""
+    s = min(64, max(1, -(-int(n) // 1024))) if slices is None else int(slices)
+    if not 1 <= s <= ANCHOR_SLICES_MAX:
+        raise ValueError(f"slices={s} outside [1, {ANCHOR_SLICES_MAX}]")
+    return s
+
+
+def anchor_wh(labels, img, shapes, scale=None):
+    """wh [n, 2] float32 = labels[:, 3:5] * (shapes[img] * scale[img]), float64 products rounded once (labels [n, 5] float64, img [n] int32,
+    shapes [n_img, 2] float64 (w, h), scale None or [n_img] float64; all on the labels' device)"""
+    n = labels.shape[0]
+    wh = torch.empty((n, 2), dtype=torch.float32, device=labels.device)
+    capi.check(capi.lib().ly_anchor_wh(_p(labels), _p(img), n, _p(shapes), shapes.shape[0], _p(scale), _p(wh), capi.stream_ptr()), "ly_anchor_wh")
+    return wh
+
+
+def anchor_metric(wh, k, thr, slices=None):
+    """-> [G, 3] float64: (sum best * (best > 1/thr), count best > 1/thr, count x > 1/thr) of every candidate set k [G, na, 2] over wh [n, 2]"""
+    n, (g, na, _) = wh.shape[0], k.shape
+    s = anchor_slices(n, slices)
+    part = torch.empty((s, 3 * g), dtype=torch.float64, device=wh.device)
+    with _Timed("ly_anchor_metric_kernel", 0.0, 8.0 * n * g):
+        capi.check(capi.lib().ly_anchor_metric(_p(wh), n, _p(k), g, na, float(thr), s, _p(part), capi.stream_ptr()), "ly_anchor_metric")
+    out = torch.empty(3 * g, dtype=torch.float64, device=wh.device)
+    capi.check(capi.lib().ly_sum_rows_f64(_p(part), s, 3 * g, _p(out), capi.stream_ptr()), "ly_sum_rows_f64")
+    return out.view(g, 3)
+
+
+def anchor_evolve_round(wh, v, k, f, cursor, batch, thr, part):
+    """one (eval, pick) pair: `batch` speculative generations from cursor[0]; part [slices, batch] float64 scratch"""
+    n, (gen, na, _), s = wh.shape[0], v.shape, part.shape[0]
+    st = capi.stream_ptr()
+    with _Timed("ly_anchor_evolve_eval_kernel", 0.0, 8.0 * n * batch):
+        capi.check(capi.lib().ly_anchor_evolve_eval(_p(wh), n, _p(v), gen, na, _p(k), _p(cursor), batch, float(thr), s, _p(part), st),
+                   "ly_anchor_evolve_eval")
+    capi.check(capi.lib().ly_anchor_evolve_pick(_p(part), s, batch, _p(v), gen, na, _p(k), _p(f), _p(cursor), st), "ly_anchor_evolve_pick")
+
+
+def kmeans_assign(pts, cent, flags, part, assign=None):
+    """the assign + accumulate half of a Lloyd iteration: part [slices, R, 3 na + 1] float64"""
+    n, (r, na, _), s = pts.shape[0], cent.shape, part.shape[0]
+    with _Timed("ly_kmeans_assign_kernel", 0.0, 8.0 * n * r):
+        capi.check(capi.lib().ly_kmeans_assign(_p(pts), n, _p(cent), r, na, _p(flags), s, _p(part), _p(assign), capi.stream_ptr()), "ly_kmeans_assign")
+
+
+def kmeans_update(part, n, thresh, cent, dist, count, flags, iters, active):
+    """the fold + update half: centroids, distortions, counts, flags, iteration counts and the open-run count, all in place"""
+    s, (r, na, _) = part.shape[0], cent.shape
+    capi.check(capi.lib().ly_kmeans_update(_p(part), s, r, na, n, float(thresh), _p(cent), _p(dist), _p(count), _p(flags), _p(iters), _p(active),
+                                           capi.stream_ptr()), "ly_kmeans_update")
