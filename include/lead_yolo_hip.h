@@ -34,14 +34,27 @@ const char* ly_last_error(void);
  * accumulators = STATISTICS PASS of the train-mode BatchNorm (sum / sum of squares of the pre-BN hidden
  * activations; y and bn_* are ignored, nothing is stored).  x and y must not alias.
  * Built for C in {16,24,40,80,160,320}. */
+/* ---- ly_<entry>_describe: the kernel a call would launch ---------------------------------------------------------------------------------
+ * Every entry point whose kernel the library picks from the shape has a describe twin.  It runs the entry's own argument checks and its own
+ * dispatch — the launch functions take a sink that is either the stream or (name, cap) — and writes the name of the contraction kernel as
+ * rocprofv3 prints it, e.g. "ly_gemm_kernel_d2<__bf16, __bf16, 4, 2, 4, 0, 0, 1, 2>", NUL-terminated, into at most cap bytes (a longer name
+ * is cut).  Host only: nothing is launched, no device is touched, no pointer is dereferenced (addresses enter the alignment tests and the
+ * null tests only).  Returns what the entry returns: 0, < 0 with ly_last_error() for arguments the entry refuses, and the entry's own
+ * positive codes.  Where a call launches several kernels (a fold after the contraction) the contraction kernel is named.
+ *   - entries that take a params struct: the same arguments with (char* name, int cap) for the stream;
+ *   - the scalar-argument MLPBlock entries: only what the plan depends on — n_img, H, W, C, dtype and the flag or pass named below;
+ *   - the other scalar-argument entries: the same arguments with (name, cap) for the stream.
+ * ly_wgrad_describe (below) states the same contract for the weight-gradient family.                                                     */
 int ly_mlpblock_fwd(const void* x /*T*/, void* y /*T*/, int n_img, int H, int W, int C, const void* wp, const void* w1,
                     const void* w2, const float* bn_scale, const float* bn_shift, double* stats, int dtype, void* stream);
+int ly_mlpblock_fwd_describe(int n_img, int H, int W, int C, int dtype, int with_stats /* the call passes stats */, char* name, int cap);
 /* The partial convolution alone: z = [conv3x3(x[:, :C/4]; wp) | x[:, C/4:]] (Partial_conv3.forward_split_cat, models/common.py:1432-1437) in one
  * read + one write of the map — what the training backward needs twice (z for the recomputed hidden tensor; with the transposed-flipped taps
  * applied to the gradient g: [d/dx of the conv | g[C/4:]]).  Persistent patch walk where the MLPBlock's applies (C < 80, W % 16 == 0, >= 1024
  * patches), the one-shot kernel stopped after the partial conv otherwise.  Returns 0 when launched, 1 for a channel count the MLPBlock
  * kernels are not built for (the caller can use a copy + ly_conv3x3_fwd), -1 on error.  x and z dense [n*H*W, C], not aliased.            */
 int ly_mlpblock_pconv(const void* x /*T*/, void* z /*T*/, int n_img, int H, int W, int C, const void* wp, int dtype, void* stream);
+int ly_mlpblock_pconv_describe(int n_img, int H, int W, int C, int dtype, char* name, int cap);      /* 1, no name: ly_mlpblock_pconv returns 1 */
 /* FUSED MLPBlock BACKWARD, bf16 storage (autograd of MLPBlock.forward + Partial_conv3.forward_split_cat, models/common.py:1432-1437, 1478-1482,
  * under train.py:327 `scaler.scale(loss).backward()`; the hidden BatchNorm in train mode).  With z = [pconv3x3(x[:, :C/4]) | x[:, C/4:]],
  * u = W1 z, v = a u + b, h = relu(v), y = x + W2 h  and  dy = d(loss)/dy:
@@ -59,6 +72,7 @@ long ly_mlpblock_bwd_slab_floats(int C);
 int ly_mlpblock_bwd(const void* x /*T*/, const void* dy /*T*/, void* g /*T*/, int n_img, int H, int W, int C, const void* wp, const void* w1,
                     const void* w2t, const void* w1t, const float* a, const float* b, const float* alpha, const float* kappa, const float* lambda,
                     double* stats, float* slab, long slab_floats, float* dw1, float* dw2, int pass, int dtype, void* stream);
+int ly_mlpblock_bwd_describe(int n_img, int H, int W, int C, int dtype, int pass, char* name, int cap);      /* the pass kernel, not pass 2's fold */
 /* The tail of the MLPBlock backward in one launch, bf16: dx = dy + [pconv^T(g[:, :C/4]) | g[:, C/4:]] (the partial conv's data gradient — wpt = the
  * transposed-flipped taps, frag-packed like wp — plus the residual of MLPBlock.forward, models/common.py:1478-1482) and, where built (2-D patches,
  * C/4 <= 32: returns 0), dwp[co * lddw + tap * dw_ts + ci * dw_cs] += sum_p g[p][co] x[p + tap][ci], the gradient of partial_conv3.weight
@@ -68,6 +82,7 @@ int ly_mlpblock_bwd(const void* x /*T*/, const void* dy /*T*/, void* g /*T*/, in
 int ly_mlpblock_bwd_dx_ok(int C, int W, int dtype);
 int ly_mlpblock_bwd_dx(const void* g /*T*/, const void* dy /*T*/, const void* x /*T*/, void* dx /*T*/, int n_img, int H, int W, int C, const void* wpt,
                        float* slab, long slab_floats, float* dwp, int lddw, int dw_ts, int dw_cs, int dtype, void* stream);
+int ly_mlpblock_bwd_dx_describe(int n_img, int H, int W, int C, int dtype, int with_dw /* the call passes slab and dwp */, char* name, int cap);
 /* hidden (2C) channel tiles of 16, padded to an even count */
 int ly_mlpblock_hidden_tiles(int C);
 
@@ -124,6 +139,7 @@ typedef struct LyGemmParams {
  * (models/common.py:1608), RFCBAMConv's k=1 path (models/rfa.py:113-129) and the FasterNet patch
  * convolutions (models/common.py:1528-1561), depending on gather/pro. */
 int ly_gemm_fwd(const LyGemmParams* p, void* stream);
+int ly_gemm_describe(const LyGemmParams* p, char* name, int cap);
 
 
 /* ---- 3x3 / s1 / p1 convolution (implicit GEMM) ------------------------------------------------- */
@@ -143,6 +159,7 @@ typedef struct LyConv3Params {
 /* Conv(c1, c2, 3, 1) = conv3x3(no bias) + BN + SiLU (CA_Bottleneck.cv2, models/common.py:1617,
  * 1890-1910). */
 int ly_conv3x3_fwd(const LyConv3Params* p, void* stream);
+int ly_conv3x3_describe(const LyConv3Params* p, char* name, int cap);
 
 
 /* ---- CoordAtt (models/common.py:1583-1609) ------------------------------------------------------- */
@@ -184,6 +201,8 @@ int ly_se_fwd(const void* x /*T*/, int ldx, int n_img, int HW, int C, const floa
  * ly_rfcbam_mid / ly_se_mlp — x is then read once instead of twice before the contraction.                              */
 int ly_rfcbam_stats(const void* x /*T*/, int ldx, int n_img, int H, int W, int C, int k, int s, const float* wg,
                     const float* a1, const float* b1, int TH, int TW, float* mm, float* part, int slices, int dtype, void* stream);
+int ly_rfcbam_stats_describe(const void* x /*T*/, int ldx, int n_img, int H, int W, int C, int k, int s, const float* wg, const float* a1, const float* b1,
+                             int TH, int TW, float* mm, float* part, int slices, int dtype, char* name, int cap);
 /* SE pooling partials alone (the first half of ly_se_fwd): part[n][slice][C] = sum of x over the pixels of slice `slice`.          */
 int ly_colsum(const void* x /*T*/, int ldx, int n_img, int HW, int C, float* part, int slices, int dtype, void* stream);
 /* SE's two linears + sigmoid from the pooling partials (-> ca [n_img, C]) and get_weight's 3x3 conv + sigmoid on the [max, mean]
@@ -213,6 +232,7 @@ typedef struct LyRfcbam3Params {
 /* RFCBAMConv kernel_size 3 main contraction (+ReLU); the k=1 case is ly_gemm_fwd with
  * LY_PRO_AFFINE_RELU_CA and rowscale = rfa.                                                         */
 int ly_rfcbam3_fwd(const LyRfcbam3Params* p, void* stream);
+int ly_rfcbam3_describe(const LyRfcbam3Params* p, char* name, int cap);
 
 /* ---- RFCBAMConv kernel_size 3 on the lane = channel core (csrc/ly_rf3c.hpp; models/rfa.py:113-129) ----------------------------
  * C % 32 == 0, stride 1 or 2, tiles TH x TW with TW even, TH*TW <= 64 and (s(TH-1)+3)(s(TW-1)+3) <= 320 input positions.
@@ -228,6 +248,7 @@ int ly_rfcbam3_fwd(const LyRfcbam3Params* p, void* stream);
 int ly_rf3c_stats(const void* x /*T*/, int ldx, int n_img, int H, int W, int C, int s, const float* wq, int raw, int TH, int TW, float* mm,
                   float* part, int slices, int dtype, void* stream);
 int ly_rf3c_fwd(const LyRfcbam3Params* p, const float* wq, int raw, void* stream);
+int ly_rf3c_fwd_describe(const LyRfcbam3Params* p, const float* wq, int raw, char* name, int cap);
 
 /* ---- RFCBAMConv kernel_size 3 with `generate` on the matrix cores (csrc/ly_rf3m.hip; models/rfa.py:113-129) --------------------------
  * bf16 storage, inference form (BatchNorm folded), C % 32 == 0, stride 1 or 2, tiles TH x TW of at most 32 output pixels that read at most
@@ -241,6 +262,7 @@ int ly_rf3c_fwd(const LyRfcbam3Params* p, const float* wq, int raw, void* stream
 int ly_rf3m_stats(const void* x /*bf16*/, int ldx, int n_img, int H, int W, int C, int s, const void* wst, int TH, int TW, float* mm, float* part,
                   int slices, void* stream);
 int ly_rf3m_fwd(const LyRfcbam3Params* p, void* stream);
+int ly_rf3m_fwd_describe(const LyRfcbam3Params* p, char* name, int cap);
 
 /* RFCBAMConv kernel_size 3 backward without 9x-sized tensors (csrc/ly_rf3c_bwd.hip; autograd of models/rfa.py:113-129): every pass
  * re-derives dcd = du . Wc^T (MFMA) and generate / BatchNorm / ReLU (VALU, bit-identical to the training forward, raw wq) on chip from
@@ -271,6 +293,9 @@ typedef struct LyRf3cBwdParams {
   int dtype;
 } LyRf3cBwdParams;
 int ly_rf3c_bwd(const LyRf3cBwdParams* p, int pass, void* stream);
+/* dynamic LDS bytes pass `pass` (0 = A, 1 = B, 2 = C) needs on TH x TW tiles of a map Wo wide with O output channels: the figure ly_rf3c_bwd
+ * itself checks against the 160 KB of a CU, for the host's tile search; < 0 for bad arguments                                            */
+int ly_rf3c_bwd_lds(int pass, int TH, int TW, int Wo, int O);
 int ly_rf3c_wgrad(const LyRf3cBwdParams* p, void* stream);
 
 
@@ -405,6 +430,7 @@ int ly_sum_rows_f64(const double* src, int R, int C, double* dst, void* stream);
  * upper triangle) of the zero-padded stride-s 3x3 taps over all n_img*Ho*Wo output pixels; mean and
  * variance of every (channel, tap-output) follow as w.m and w^T M w on the host.                        */
 int ly_rfcbam_tap_moments(const void* x /*T*/, int ldx, int n_img, int H, int W, int C, int s, double* mom /* [54][C] doubles, zeroed */, int dtype, void* stream);
+int ly_rfcbam_tap_moments_describe(const void* x /*T*/, int ldx, int n_img, int H, int W, int C, int s, double* mom, int dtype, char* name, int cap);
 /* Train-mode `generate` BatchNorm of RFCBAMConv (models/rfa.py:101-106) from those moments (k = 3: mom [54][C]; k = 1: ly_chan_moments'
  * [2][C]) and generate.0.weight, ONE launch: batch statistics of every generate channel g = c*k*k + t, running statistics and
  * num_batches_tracked updated as nn.BatchNorm2d does (NULL = not tracked);
@@ -630,6 +656,8 @@ int ly_patch4_rows_u8(const unsigned char* img, int n_img, int C, int H, int W, 
  * (ly_sum_rows): no atomics.  scale = 1/255 for the `imgs / 255` of train.py:309.                                                           */
 int ly_patch4_wgrad_u8(const unsigned char* img, int n_img, int C, int H, int W, const void* du /*bf16*/, int lddu, int N, float scale, float* slab,
                        long slab_floats, float* dw /*[N][16*C], += */, int dtype, void* stream);
+int ly_patch4_wgrad_u8_describe(const unsigned char* img, int n_img, int C, int H, int W, const void* du /*bf16*/, int lddu, int N, float scale, float* slab,
+                                long slab_floats, float* dw, int dtype, char* name, int cap);
 
 /* CoordAtt backward (models/common.py:1595-1609).  Gate out = x*a_h[n,h,:]*a_w[n,w,:]:
  *   dx = dout*a_h*a_w,  da_h[n,h,c] = sum_w dout*x*a_w,  da_w[n,w,c] = sum_h dout*x*a_h — written as PARTIAL sums, one plain store per
@@ -684,6 +712,8 @@ int ly_rf_bwd_gen(const void* x /*T*/, int ldx, int n_img, int H, int W, int C, 
 int ly_rf_bwd_dx(int n_img, int H, int W, int C, int k, int s, const void* dug /*T*/, const float* wg, void* dx /*T*/, int lddx,
                  const float* addnc /* NULL, or [n_img, C]: dx += addnc[n, c] * add_scale (the SE pooling's gradient) */, float add_scale,
                  int dtype, void* stream);
+int ly_rf_bwd_dx_describe(int n_img, int H, int W, int C, int k, int s, const void* dug /*T*/, const float* wg, void* dx /*T*/, int lddx, const float* addnc,
+                          float add_scale, int dtype, char* name, int cap);
 /* SE backward in training (models/rfa.py:88-92), two launches: from the forward's pooling partials part[n][slices][C] (HW pixels per
  * image), ca = sigmoid(wb relu(wa mean)) and d_ca: dwa [R, C], dwb [C, R] are ADDED TO (one thread per weight sums the per-image outer
  * products kept in ws: no atomics, deterministic), dgap [n_img, C] = d/d(mean x) is written.  ws: scratch, n_img * (2C + 2R) floats. */

@@ -395,15 +395,18 @@ __global__ __launch_bounds__(LY_THREADS) void ly_rfcbam_pre1v_kernel(const T* __
 }
 
 template <typename T>
-static bool pre1v_launch(const T* x, int ldx, int n_img, int HW, int C, int slices, const float* a1, const float* b1, float* mm, float* part, hipStream_t st) {
+static int pre1v_launch(const T* x, int ldx, int n_img, int HW, int C, int slices, const float* a1, const float* b1, float* mm, float* part, const LyOut& out) {
   constexpr int VW = LyT<T>::VW;
-  if (C % VW || ldx % VW) return false;
+  if (C % VW || ldx % VW) return 1;                             // 1: not this kernel's shape
   const int nv = C / VW, vpl = (nv + 15) / 16;
   const size_t lds = (size_t)16 * C * sizeof(float);            // 16 pixel groups per block
-#define LY_PV(V_) case V_: hipLaunchKernelGGL((ly_rfcbam_pre1v_kernel<T, V_>), dim3((unsigned)(n_img * slices)), dim3(LY_THREADS), lds, st, x, ldx, HW, C, slices, a1, b1, mm, part); return true
+#define LY_PV(V_)                                                                                                                                                  \
+  case V_:                                                                                                                                                         \
+    return LY_EMIT(out, (ly_launch<ly_rfcbam_pre1v_kernel<T, V_>>(dim3((unsigned)(n_img * slices)), dim3(LY_THREADS), lds, out.st, x, ldx, HW, C, slices, a1, b1, mm, part)), \
+                   "ly_rfcbam_pre1v_kernel<%s, " #V_ ">", ly_tname<T>())
   switch (vpl) { LY_PV(1); LY_PV(2); LY_PV(3); LY_PV(4); default: break; }
 #undef LY_PV
-  return false;
+  return 1;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -586,29 +589,27 @@ __global__ __launch_bounds__(LY_THREADS) void ly_rfcbam_stats3_kernel(const T* _
   }
 }
 
-extern "C" int ly_rfcbam_stats(const void* x, int ldx, int n_img, int H, int W, int C, int k, int s, const float* wg,
-                               const float* a1, const float* b1, int TH, int TW, float* mm, float* part, int slices, int dtype, void* stream) {
+static int rfcbam_stats_entry(const void* x, int ldx, int n_img, int H, int W, int C, int k, int s, const float* wg, const float* a1, const float* b1, int TH,
+                              int TW, float* mm, float* part, int slices, int dtype, const LyOut& out) {
   LY_CHECK_DTYPE(dtype, "rfcbam_stats");
   LY_CHECK(x && mm && (C & 3) == 0 && (ldx & 3) == 0, "rfcbam_stats: bad arguments");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (k == 1) {
     LY_CHECK(s == 1 && a1 && b1, "rfcbam_stats: k=1 needs stride 1 and folded scale/shift");
     long M = (long)n_img * H * W;
     if (part) {           // statistics + SE pooling partials in one pass
       LY_CHECK(slices > 0 && C <= 256 * LY_PRE1_NS, "rfcbam_stats: fused SE pooling needs slices > 0 and C <= %d", 256 * LY_PRE1_NS);
-      bool done = false;
-      LY_WITH_T(dtype, done = pre1v_launch<T>(reinterpret_cast<const T*>(x), ldx, n_img, H * W, C, slices, a1, b1, mm, part, st));      // several pixels per wave
-      if (!done)
-        LY_WITH_T(dtype, hipLaunchKernelGGL(ly_rfcbam_pre1_kernel<T>, dim3((unsigned)(n_img * slices)), dim3(LY_THREADS), 0, st, reinterpret_cast<const T*>(x), ldx,
-                                            H * W, C, slices, a1, b1, mm, part));
-      LY_LAUNCH_CHECK();
-      return 0;
+      int rc = 1;
+      LY_WITH_T(dtype, rc = pre1v_launch<T>(reinterpret_cast<const T*>(x), ldx, n_img, H * W, C, slices, a1, b1, mm, part, out));      // several pixels per wave
+      if (rc != 1) return rc;
+      LY_WITH_T(dtype, return LY_EMIT(out, (ly_launch<ly_rfcbam_pre1_kernel<T>>(dim3((unsigned)(n_img * slices)), dim3(LY_THREADS), 0, out.st, reinterpret_cast<const T*>(x),
+                                                                                ldx, H * W, C, slices, a1, b1, mm, part)),
+                                      "ly_rfcbam_pre1_kernel<%s>", ly_tname<T>()));
     }
     long blocks = (M + 3) / 4;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    LY_WITH_T(dtype, hipLaunchKernelGGL(ly_rfcbam_stats1_kernel<T>, dim3((unsigned)blocks), dim3(LY_THREADS), 0, st, reinterpret_cast<const T*>(x), ldx, M, C, a1, b1, mm));
-    LY_LAUNCH_CHECK();
-    return 0;
+    LY_WITH_T(dtype, return LY_EMIT(out, (ly_launch<ly_rfcbam_stats1_kernel<T>>(dim3((unsigned)blocks), dim3(LY_THREADS), 0, out.st, reinterpret_cast<const T*>(x), ldx, M, C,
+                                                                                a1, b1, mm)),
+                                    "ly_rfcbam_stats1_kernel<%s>", ly_tname<T>()));
   }
   LY_CHECK(k == 3 && s >= 1 && wg, "rfcbam_stats: only k in {1,3} is built");
   LY_CHECK(TW >= 1 && TH >= 1 && TH * TW <= 64, "rfcbam_stats: tile %dx%d does not fit a wave", TH, TW);
@@ -619,8 +620,21 @@ extern "C" int ly_rfcbam_stats(const void* x, int ldx, int n_img, int H, int W, 
   size_t lds = sizeof(float) * ((size_t)4 * LY_ST3_WF + (size_t)IH * IW * (LY_SCC + 1) + 4 * 18 * 64);
   LY_CHECK(IH * IW * (LY_SCC / 4) <= LY_ST3_NV * LY_THREADS, "rfcbam_stats: input tile %dx%d exceeds the staging capacity", IH, IW);
   LY_CHECK(lds <= LY_LDS_MAX, "rfcbam_stats: tile needs %zu B LDS", lds);
-  LY_WITH_T(dtype, return ly_launch_lds<ly_rfcbam_stats3_kernel<T>>(dim3(n_img * nrt * nct), dim3(LY_THREADS), lds, st, reinterpret_cast<const T*>(x), ldx, H, W, C,
-                                                                    Ho, Wo, s, TH, TW, nct, nrt, wg, mm, part));
+  LY_WITH_T(dtype, return LY_EMIT(out, (ly_launch_lds<ly_rfcbam_stats3_kernel<T>>(dim3(n_img * nrt * nct), dim3(LY_THREADS), lds, out.st, reinterpret_cast<const T*>(x), ldx,
+                                                                                  H, W, C, Ho, Wo, s, TH, TW, nct, nrt, wg, mm, part)),
+                                  "ly_rfcbam_stats3_kernel<%s>", ly_tname<T>()));
+}
+
+extern "C" int ly_rfcbam_stats(const void* x, int ldx, int n_img, int H, int W, int C, int k, int s, const float* wg,
+                               const float* a1, const float* b1, int TH, int TW, float* mm, float* part, int slices, int dtype, void* stream) {
+  return rfcbam_stats_entry(x, ldx, n_img, H, W, C, k, s, wg, a1, b1, TH, TW, mm, part, slices, dtype, LY_ON_STREAM(stream));
+}
+
+// the arguments of ly_rfcbam_stats with (name, cap) for the stream
+extern "C" int ly_rfcbam_stats_describe(const void* x, int ldx, int n_img, int H, int W, int C, int k, int s, const float* wg, const float* a1, const float* b1, int TH,
+                                        int TW, float* mm, float* part, int slices, int dtype, char* name, int cap) {
+  LY_CHECK(name && cap > 0, "rfcbam_stats_describe: bad arguments");
+  return rfcbam_stats_entry(x, ldx, n_img, H, W, C, k, s, wg, a1, b1, TH, TW, mm, part, slices, dtype, LyOut{nullptr, name, cap});
 }
 
 // rfa[n, y, x] = sigmoid( sum_{ch, dy, dx} w[ch][dy][dx] * mm[n, y+dy-1, x+dx-1, ch] )
@@ -1336,7 +1350,7 @@ __global__ __launch_bounds__(LY_THREADS) void ly_rfcbam_tap_moments_s2t_kernel(c
   (void)cok;
 }
 
-extern "C" int ly_rfcbam_tap_moments(const void* x, int ldx, int n_img, int H, int W, int C, int s, double* mom, int dtype, void* stream) {
+static int tap_moments_entry(const void* x, int ldx, int n_img, int H, int W, int C, int s, double* mom, int dtype, const LyOut& out) {
   LY_CHECK_DTYPE(dtype, "rfcbam_tap_moments");
   LY_CHECK(x && mom && s >= 1 && C > 0, "rfcbam_tap_moments: bad arguments");
   const int Ho = (H + 2 - 3) / s + 1, Wo = (W + 2 - 3) / s + 1;
@@ -1351,16 +1365,25 @@ extern "C" int ly_rfcbam_tap_moments(const void* x, int ldx, int n_img, int H, i
     constexpr int NPX = (2 * LY_TM_T + 1) * (2 * LY_TM_T + 1);
     size_t lds = (size_t)NPX * 64 * esz;
     if (lds < 4 * 27 * 64 * sizeof(float)) lds = 4 * 27 * 64 * sizeof(float);
-    LY_WITH_T(dtype, return ly_launch_lds<ly_rfcbam_tap_moments_s2t_kernel<T>>(dim3((unsigned)nb, (unsigned)groups), dim3(LY_THREADS), lds,
-                                                                               reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const T*>(x), ldx,
-                                                                               n_img, H, W, C, Ho, Wo, tiles_y, tiles_x, mom));
+    LY_WITH_T(dtype, return LY_EMIT(out, (ly_launch_lds<ly_rfcbam_tap_moments_s2t_kernel<T>>(dim3((unsigned)nb, (unsigned)groups), dim3(LY_THREADS), lds, out.st,
+                                                                                             reinterpret_cast<const T*>(x), ldx, n_img, H, W, C, Ho, Wo, tiles_y, tiles_x, mom)),
+                                    "ly_rfcbam_tap_moments_s2t_kernel<%s>", ly_tname<T>()));
   }
   long blocks = npix / 32 + 1;
   if (blocks > 1024) blocks = 1024;
-  LY_WITH_T(dtype, hipLaunchKernelGGL(ly_rfcbam_tap_moments_kernel<T>, dim3((unsigned)blocks), dim3(LY_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
-                                      reinterpret_cast<const T*>(x), ldx, n_img, H, W, C, Ho, Wo, s, mom));
-  LY_LAUNCH_CHECK();
-  return 0;
+  LY_WITH_T(dtype, return LY_EMIT(out, (ly_launch<ly_rfcbam_tap_moments_kernel<T>>(dim3((unsigned)blocks), dim3(LY_THREADS), 0, out.st, reinterpret_cast<const T*>(x), ldx,
+                                                                                   n_img, H, W, C, Ho, Wo, s, mom)),
+                                  "ly_rfcbam_tap_moments_kernel<%s>", ly_tname<T>()));
+}
+
+extern "C" int ly_rfcbam_tap_moments(const void* x, int ldx, int n_img, int H, int W, int C, int s, double* mom, int dtype, void* stream) {
+  return tap_moments_entry(x, ldx, n_img, H, W, C, s, mom, dtype, LY_ON_STREAM(stream));
+}
+
+// the arguments of ly_rfcbam_tap_moments with (name, cap) for the stream
+extern "C" int ly_rfcbam_tap_moments_describe(const void* x, int ldx, int n_img, int H, int W, int C, int s, double* mom, int dtype, char* name, int cap) {
+  LY_CHECK(name && cap > 0, "rfcbam_tap_moments_describe: bad arguments");
+  return tap_moments_entry(x, ldx, n_img, H, W, C, s, mom, dtype, LyOut{nullptr, name, cap});
 }
 
 // ---------------------------------------------------------------------------------------------------

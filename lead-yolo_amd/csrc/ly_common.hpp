@@ -23,6 +23,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <type_traits>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -278,6 +280,42 @@ struct LyDevOnce {
     if (r_) return r_;                     \
   } while (0)
 
+// Where a launch goes: onto the stream — or, with `name` set (the ly_*_describe entry points), nowhere: only the contraction kernel's name
+// as rocprofv3 prints it, NUL-terminated in at most `cap` bytes.  A launch function takes a LyOut where it would take the stream, and
+// LY_EMIT stands at its leaf, where every template argument of the instantiation is in scope: the name is written next to the kernel it
+// describes and nothing restates the dispatch.  A description returns before anything that needs a device (ly_lds_allow, occupancy queries).
+struct LyOut {
+  hipStream_t st;
+  char* name;
+  int cap;
+};
+#define LY_EMIT(out, launch, ...) ((out).name ? (snprintf((out).name, (size_t)(out).cap, __VA_ARGS__), 0) : (launch))
+// the same ahead of a launch that first asks the device something: a description leaves the function here
+#define LY_DESCRIBED(out, ...)                                     \
+  do {                                                             \
+    if ((out).name) {                                              \
+      snprintf((out).name, (size_t)(out).cap, __VA_ARGS__);        \
+      return 0;                                                    \
+    }                                                              \
+  } while (0)
+#define LY_ON_STREAM(stream) LyOut{reinterpret_cast<hipStream_t>(stream), nullptr, 0}
+#define LY_BOOL(b) ((b) ? "true" : "false")
+
+// a storage / image element type as rocprofv3 spells it in a kernel's template arguments
+struct ly_bf16img;
+struct ly_f16img;
+template <typename T>
+constexpr const char* ly_tname() {
+  if constexpr (std::is_same_v<T, float>) return "float";
+  else if constexpr (std::is_same_v<T, __bf16>) return "__bf16";
+  else if constexpr (std::is_same_v<T, unsigned char>) return "unsigned char";
+  else if constexpr (std::is_same_v<T, ly_bf16img>) return "ly_bf16img";
+  else {
+    static_assert(std::is_same_v<T, ly_f16img>, "ly_tname: no spelling for this type");
+    return "ly_f16img";
+  }
+}
+
 // The LDS of one gfx950 CU: the most dynamic LDS a launch may ask for
 constexpr size_t LY_LDS_MAX = 160 * 1024;
 
@@ -292,6 +330,13 @@ int ly_lds_allow() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LY_LDS_MAX);
     LY_CHECK(e == hipSuccess, "cannot raise a kernel's dynamic LDS cap to %zu B: %s", LY_LDS_MAX, hipGetErrorString(e));
   }
+  return 0;
+}
+// a plain launch (no LDS cap raised: `lds` within the 64 KB default) as an expression, which is what LY_EMIT takes
+template <auto KERNEL, class... A>
+int ly_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+  hipLaunchKernelGGL(KERNEL, grid, block, lds, st, args...);
+  LY_LAUNCH_CHECK();
   return 0;
 }
 template <auto KERNEL, class... A>

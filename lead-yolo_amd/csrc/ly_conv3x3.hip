@@ -526,7 +526,7 @@ static int conv3_row_pitch(int TH, int TW, int rsh) {
 }
 
 template <typename T, int MT, int WC, bool LAT = false, int NTA = 0>
-static int launch_conv3(const LyConv3Params& P, hipStream_t st) {
+static int launch_conv3(const LyConv3Params& P, const LyOut& out) {
   const int tiles_x = (P.W + P.TW - 1) / P.TW, tiles_y = (P.H + P.TH - 1) / P.TH;
   const int gy = (P.N + 16 * MT * WC - 1) / (16 * MT * WC);
   const long n_img = P.M / ((long)P.H * P.W);
@@ -535,12 +535,16 @@ static int launch_conv3(const LyConv3Params& P, hipStream_t st) {
   const int rp = conv3_row_pitch(P.TH, P.TW, ly_qrs(8 * LyT<T>::VW / 32));
   const int ps = ly_qps((P.TH + 2) * rp);
   size_t lds = LyT<T>::PL * (size_t)4 * ps;
-  if constexpr (LAT) return ly_launch_lds<ly_conv3x3_lat_kernel<T, MT, WC>>(dim3((unsigned)nb), dim3(LY_THREADS), lds, st, P, gy, tiles_x, tiles_y, rp, ps);
-  else return ly_launch_lds<ly_conv3x3_kernel<T, MT, WC, NTA>>(dim3((unsigned)nb), dim3(LY_THREADS), lds, st, P, gy, tiles_x, tiles_y, rp, ps);
+  if constexpr (LAT)
+    return LY_EMIT(out, (ly_launch_lds<ly_conv3x3_lat_kernel<T, MT, WC>>(dim3((unsigned)nb), dim3(LY_THREADS), lds, out.st, P, gy, tiles_x, tiles_y, rp, ps)),
+                   "ly_conv3x3_lat_kernel<%s, %d, %d>", ly_tname<T>(), MT, WC);
+  else
+    return LY_EMIT(out, (ly_launch_lds<ly_conv3x3_kernel<T, MT, WC, NTA>>(dim3((unsigned)nb), dim3(LY_THREADS), lds, out.st, P, gy, tiles_x, tiles_y, rp, ps)),
+                   "ly_conv3x3_kernel<%s, %d, %d, %d>", ly_tname<T>(), MT, WC, NTA);
 }
 
 template <typename T>
-static int conv3_dispatch(const LyConv3Params& P, hipStream_t st) {
+static int conv3_dispatch(const LyConv3Params& P, const LyOut& out) {
   // measured on MI355X: 32 channels per wave is the sweet spot at every LEAD-YOLO shape
 #ifdef LY_DEVEL
   static int mode = -1;                                   // development builds (make DEVEL=1) read LY_C3_MODE: 1 = <2,4>, 2 = <2,4,LAT>, 3 = <2,2>, 4 = <2,2,LAT>
@@ -551,25 +555,25 @@ static int conv3_dispatch(const LyConv3Params& P, hipStream_t st) {
   if constexpr (LyT<T>::BF) {
     const long tiles = (P.M / ((long)P.H * P.W)) * ((P.W + P.TW - 1) / P.TW) * ((P.H + P.TH - 1) / P.TH);
     const bool small = tiles * ((P.N + 127) / 128) < 2 * 256;            // fewer than two blocks per CU
-    if (mode == 2) return launch_conv3<T, 2, 4, true>(P, st);
-    if (mode == 4 || (mode == 0 && P.N > 64 && small)) return launch_conv3<T, 2, 2, true>(P, st);   // 64 channels per block: twice the blocks
+    if (mode == 2) return launch_conv3<T, 2, 4, true>(P, out);
+    if (mode == 4 || (mode == 0 && P.N > 64 && small)) return launch_conv3<T, 2, 2, true>(P, out);   // 64 channels per block: twice the blocks
   }
   const int ntv = (P.TH * P.TW + 15) >> 4;                // active pixel tiles of a patch
-  if (mode == 3) return launch_conv3<T, 2, 2>(P, st);
+  if (mode == 3) return launch_conv3<T, 2, 2>(P, out);
   if (mode == 1 || P.N > 64) {                            // 4 waves x 32 ch (128 ch per block), all 8 pixel tiles each
     if constexpr (LyT<T>::BF) {
-      if (mode == 0 && ntv == 5) return launch_conv3<T, 2, 4, false, 5>(P, st);
-      if (mode == 0 && ntv == 8) return launch_conv3<T, 2, 4, false, 8>(P, st);
+      if (mode == 0 && ntv == 5) return launch_conv3<T, 2, 4, false, 5>(P, out);
+      if (mode == 0 && ntv == 8) return launch_conv3<T, 2, 4, false, 8>(P, out);
     }
-    return launch_conv3<T, 2, 4>(P, st);
+    return launch_conv3<T, 2, 4>(P, out);
   }
   if constexpr (LyT<T>::BF) {
-    if (mode == 0 && ntv == 8) return launch_conv3<T, 2, 2, false, 4>(P, st);
+    if (mode == 0 && ntv == 8) return launch_conv3<T, 2, 2, false, 4>(P, out);
   }
-  return launch_conv3<T, 2, 2>(P, st);                    // 2 x 32 ch, 2 pixel groups of 4 tiles
+  return launch_conv3<T, 2, 2>(P, out);                    // 2 x 32 ch, 2 pixel groups of 4 tiles
 }
 
-extern "C" int ly_conv3x3_fwd(const LyConv3Params* p, void* stream) {
+static int conv3_entry(const LyConv3Params* p, const LyOut& out) {
   LY_CHECK(p, "conv3x3: null params");
   const LyConv3Params& P = *p;
   LY_CHECK(P.dtype == LY_F32 || P.dtype == LY_BF16, "conv3x3: unknown dtype %d", P.dtype);
@@ -582,6 +586,12 @@ extern "C" int ly_conv3x3_fwd(const LyConv3Params* p, void* stream) {
   LY_CHECK(P.TH >= 1 && P.TW >= 1 && P.TH * P.TW <= 16 * LY_C3_NT, "conv3x3: patch %dx%d exceeds %d pixels", P.TH, P.TW, 16 * LY_C3_NT);
   LY_CHECK((P.TH + 2) * (P.TW + 2) * 8 <= LY_C3_NV * LY_THREADS, "conv3x3: frame of patch %dx%d exceeds the staging capacity", P.TH, P.TW);
   LY_CHECK(P.M * (long)P.ldx < (1L << 31), "conv3x3: input exceeds the 31-bit offsets of the staging plan");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return P.dtype == LY_BF16 ? conv3_dispatch<__bf16>(P, st) : conv3_dispatch<float>(P, st);
+  return P.dtype == LY_BF16 ? conv3_dispatch<__bf16>(P, out) : conv3_dispatch<float>(P, out);
+}
+
+extern "C" int ly_conv3x3_fwd(const LyConv3Params* p, void* stream) { return conv3_entry(p, LY_ON_STREAM(stream)); }
+
+extern "C" int ly_conv3x3_describe(const LyConv3Params* p, char* name, int cap) {
+  LY_CHECK(name && cap > 0, "conv3x3_describe: bad arguments");
+  return conv3_entry(p, LyOut{nullptr, name, cap});
 }

@@ -2,9 +2,10 @@
 // bf16-storage instantiations are in ly_gemm_bf16.hip — two translation units only to build them in parallel).
 #include "ly_gemm.hpp"
 
-int ly_gemm_dispatch_f32(const LyGemmParams& P, hipStream_t st) { return ly_gemm_dispatch<float>(P, st); }
+int ly_gemm_dispatch_f32(const LyGemmParams& P, const LyOut& out) { return ly_gemm_dispatch<float>(P, out); }
 
-extern "C" int ly_gemm_fwd(const LyGemmParams* p, void* stream) {
+// ly_gemm_fwd and its description: the checks, then the dispatch onto the stream or into the name
+static int gemm_entry(const LyGemmParams* p, const LyOut& out) {
   LY_CHECK(p, "gemm: null params");
   const LyGemmParams& P = *p;
   LY_CHECK(P.dtype == LY_F32 || P.dtype == LY_BF16, "gemm: unknown dtype %d", P.dtype);
@@ -39,7 +40,7 @@ extern "C" int ly_gemm_fwd(const LyGemmParams* p, void* stream) {
     Q.scat_ks = 1;
     Q.scat_c = (P.N + 3) & ~3;
     LY_CHECK((P.N & 3) == 0, "gemm: eadd needs N %% 4 == 0 (N=%d)", P.N);
-    return ly_gemm_fwd(&Q, stream);
+    return gemm_entry(&Q, out);
   }
   if (P.eadd) LY_CHECK(P.ldeadd >= P.scat_c && (P.ldeadd & 3) == 0 && ((uintptr_t)P.eadd & (P.dtype == LY_BF16 ? 7 : 15)) == 0, "gemm: eadd must be a 4-element aligned row matrix (ldeadd=%d)", P.ldeadd);
   if (P.scat_ks) {
@@ -49,10 +50,14 @@ extern "C" int ly_gemm_fwd(const LyGemmParams* p, void* stream) {
     LY_CHECK(P.gather == LY_GATHER_ROWS && P.pro == LY_PRO_NONE && !P.stats && P.out && (P.ldo & 3) == 0 && P.M == (long)(P.M / ((long)P.H * P.W)) * P.H * P.W,
              "gemm: scatter store is built for plain-row sources without prologue / statistics, M a whole number of H x W maps");
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (ly_patch4_try(P, st)) {                              // PatchEmbed on an RGB image: its own LDS-free kernel (ly_patch4.hip)
-    LY_LAUNCH_CHECK();
-    return 0;
-  }
-  return P.dtype == LY_BF16 ? ly_gemm_dispatch_bf16(P, st) : ly_gemm_dispatch_f32(P, st);
+  const int p4 = ly_patch4_try(P, out);                    // PatchEmbed on an RGB image: its own LDS-free kernel (ly_patch4.hip)
+  if (p4) return p4 < 0 ? p4 : 0;
+  return P.dtype == LY_BF16 ? ly_gemm_dispatch_bf16(P, out) : ly_gemm_dispatch_f32(P, out);
+}
+
+extern "C" int ly_gemm_fwd(const LyGemmParams* p, void* stream) { return gemm_entry(p, LY_ON_STREAM(stream)); }
+
+extern "C" int ly_gemm_describe(const LyGemmParams* p, char* name, int cap) {
+  LY_CHECK(name && cap > 0, "gemm_describe: bad arguments");
+  return gemm_entry(p, LyOut{nullptr, name, cap});
 }

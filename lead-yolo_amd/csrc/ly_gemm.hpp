@@ -504,7 +504,7 @@ __global__ __launch_bounds__(LY_THREADS) __attribute__((amdgpu_waves_per_eu(LY_G
 }
 
 template <typename TI, typename TO, int NT, int MT, int WC, int GATHER, int PRO, int NCH = 0, int FAST = 0>
-static int launch_gemm_d2(const LyGemmParams& P, hipStream_t st) {
+static int launch_gemm_d2(const LyGemmParams& P, const LyOut& out) {
   constexpr int BP = 16 * NT * (4 / WC);
   constexpr int BN = 16 * MT * WC;
   constexpr int BK = 16 * LyT<TI>::VW;
@@ -513,6 +513,7 @@ static int launch_gemm_d2(const LyGemmParams& P, hipStream_t st) {
   int gy = (P.N + BN - 1) / BN;
   LY_CHECK(gx < (1L << 30), "gemm: too many pixel tiles");
   constexpr auto k = ly_gemm_kernel_d2<TI, TO, NT, MT, WC, GATHER, PRO, NCH, FAST>;
+  LY_DESCRIBED(out, "ly_gemm_kernel_d2<%s, %s, %d, %d, %d, %d, %d, %d, %d>", ly_tname<TI>(), ly_tname<TO>(), NT, MT, WC, GATHER, PRO, NCH, FAST);
   static int per_cu = 0;            // co-resident blocks per CU (registers + LDS), measured once per instantiation
   if (per_cu == 0) {
     LY_TRY(ly_lds_allow<k>());      // ahead of the occupancy query
@@ -525,14 +526,14 @@ static int launch_gemm_d2(const LyGemmParams& P, hipStream_t st) {
   long nslots = (256L * per_cu) / gy;
   if (nslots < 1) nslots = 1;
   if (nslots > gx) nslots = gx;
-  return ly_launch_lds<k>(dim3((unsigned)(nslots * gy)), dim3(LY_THREADS), lds, st, P, gy, (int)nslots, (int)gx);
+  return ly_launch_lds<k>(dim3((unsigned)(nslots * gy)), dim3(LY_THREADS), lds, out.st, P, gy, (int)nslots, (int)gx);
 }
 
 // Variant choice per call.  K in one or two chunks: weights resident (NCH) and, when every channel tile is full and the stores can be
 // vectors, the branch-free epilogue (FAST 1; 2 = with the BatchNorm sums of the training forward kept in registers; 3 = FAST 1 with the
 // scatter store of LyGemmParams.scat_ks; 4 = 3 + LyGemmParams.eadd added before the store).
 template <typename TI, typename TO, int NT, int MT, int WC, int GATHER, int PRO>
-static int launch_gemm_v(const LyGemmParams& P, hipStream_t st) {
+static int launch_gemm_v(const LyGemmParams& P, const LyOut& out) {
   // which of the variants fit 256 registers without spilling into the loop (checked in the .s of every instantiation)
   constexpr bool ok1 = WC == 4 || PRO == LY_PRO_NONE;                  // one chunk resident
   constexpr bool ok2 = WC == 4 && PRO != LY_PRO_GATE;                  // two chunks resident
@@ -543,70 +544,70 @@ static int launch_gemm_v(const LyGemmParams& P, hipStream_t st) {
   if (P.scat_ks) {                                          // scatter store (ly_gemm_fwd checked: plain rows, no prologue, no statistics, fast widths)
     if constexpr (GATHER == LY_GATHER_ROWS && PRO == LY_PRO_NONE) {
       if (P.eadd) {
-        if constexpr (ok1) { if (nchunk == 1) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 1, 4>(P, st); }
-        if constexpr (ok2) { if (nchunk == 2) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 2, 4>(P, st); }
-        return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 0, 4>(P, st);
+        if constexpr (ok1) { if (nchunk == 1) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 1, 4>(P, out); }
+        if constexpr (ok2) { if (nchunk == 2) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 2, 4>(P, out); }
+        return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 0, 4>(P, out);
       }
-      if constexpr (ok1) { if (nchunk == 1) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 1, 3>(P, st); }
-      if constexpr (ok2) { if (nchunk == 2) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 2, 3>(P, st); }
-      return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 0, 3>(P, st);
+      if constexpr (ok1) { if (nchunk == 1) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 1, 3>(P, out); }
+      if constexpr (ok2) { if (nchunk == 2) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 2, 3>(P, out); }
+      return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 0, 3>(P, out);
     } else {
       ly_set_error("gemm: the scatter store is built for plain-row sources without a prologue");
       return -1;
     }
   }
   if (fast && !P.stats) {
-    if constexpr (ok1) { if (nchunk == 1) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 1, 1>(P, st); }
-    if constexpr (ok2) { if (nchunk == 2) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 2, 1>(P, st); }
+    if constexpr (ok1) { if (nchunk == 1) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 1, 1>(P, out); }
+    if constexpr (ok2) { if (nchunk == 2) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 2, 1>(P, out); }
   } else if (fast) {
-    if constexpr (oks1) { if (nchunk == 1) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 1, 2>(P, st); }
-    if constexpr (oks2) { if (nchunk == 2) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 2, 2>(P, st); }
+    if constexpr (oks1) { if (nchunk == 1) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 1, 2>(P, out); }
+    if constexpr (oks2) { if (nchunk == 2) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 2, 2>(P, out); }
   }
   if constexpr (PRO == LY_PRO_GATE) {                      // CoordAtt-gate GEMM with K in more than one chunk (eval C3_CA.cv3): the branch-free epilogue
-    if (fast && !P.stats) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 0, 1>(P, st);
+    if (fast && !P.stats) return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 0, 1>(P, out);
   }
   if constexpr (PRO == LY_PRO_NONE) {                      // long K: weights streamed one item ahead, still the branch-free epilogue
-    if (fast) return P.stats ? launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 0, 2>(P, st) : launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 0, 1>(P, st);
+    if (fast) return P.stats ? launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 0, 2>(P, out) : launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO, 0, 1>(P, out);
   }
-  return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO>(P, st);
+  return launch_gemm_d2<TI, TO, NT, MT, WC, GATHER, PRO>(P, out);
 }
 
 template <typename T, int NT, int MT, int WC>
-static int launch_gemm(const LyGemmParams& P, hipStream_t st) {
-  if (P.gather == LY_GATHER_PATCH) return launch_gemm_v<T, T, NT, MT, WC, LY_GATHER_PATCH, LY_PRO_NONE>(P, st);
-  if (P.gather == LY_GATHER_PATCH_NCHW) return launch_gemm_v<float, T, NT, MT, WC, LY_GATHER_PATCH_NCHW, LY_PRO_NONE>(P, st);
-  if (P.gather == LY_GATHER_PATCH_NCHW_U8) return launch_gemm_v<unsigned char, T, NT, MT, WC, LY_GATHER_PATCH_NCHW, LY_PRO_NONE>(P, st);
+static int launch_gemm(const LyGemmParams& P, const LyOut& out) {
+  if (P.gather == LY_GATHER_PATCH) return launch_gemm_v<T, T, NT, MT, WC, LY_GATHER_PATCH, LY_PRO_NONE>(P, out);
+  if (P.gather == LY_GATHER_PATCH_NCHW) return launch_gemm_v<float, T, NT, MT, WC, LY_GATHER_PATCH_NCHW, LY_PRO_NONE>(P, out);
+  if (P.gather == LY_GATHER_PATCH_NCHW_U8) return launch_gemm_v<unsigned char, T, NT, MT, WC, LY_GATHER_PATCH_NCHW, LY_PRO_NONE>(P, out);
   if (P.gather == LY_GATHER_PATCH_NCHW_BF16 || P.gather == LY_GATHER_PATCH_NCHW_F16) {
     if constexpr (LyT<T>::BF) {
-      if (P.gather == LY_GATHER_PATCH_NCHW_BF16) return launch_gemm_v<ly_bf16img, T, NT, MT, WC, LY_GATHER_PATCH_NCHW, LY_PRO_NONE>(P, st);
-      return launch_gemm_v<ly_f16img, T, NT, MT, WC, LY_GATHER_PATCH_NCHW, LY_PRO_NONE>(P, st);
+      if (P.gather == LY_GATHER_PATCH_NCHW_BF16) return launch_gemm_v<ly_bf16img, T, NT, MT, WC, LY_GATHER_PATCH_NCHW, LY_PRO_NONE>(P, out);
+      return launch_gemm_v<ly_f16img, T, NT, MT, WC, LY_GATHER_PATCH_NCHW, LY_PRO_NONE>(P, out);
     } else {
       ly_set_error("gemm: a 16-bit image source is built for LY_BF16 calls only");
       return -1;
     }
   }
   if (P.gather == LY_GATHER_UP2) {
-    if (P.pro == LY_PRO_NONE) return launch_gemm_v<T, T, NT, MT, WC, LY_GATHER_UP2, LY_PRO_NONE>(P, st);
+    if (P.pro == LY_PRO_NONE) return launch_gemm_v<T, T, NT, MT, WC, LY_GATHER_UP2, LY_PRO_NONE>(P, out);
     ly_set_error("gemm: upsampled source with a prologue is not built");
     return -1;
   }
-  if (P.pro == LY_PRO_GATE) return launch_gemm_v<T, T, NT, MT, WC, LY_GATHER_ROWS, LY_PRO_GATE>(P, st);
-  if (P.pro == LY_PRO_AFFINE_RELU_CA) return launch_gemm_v<T, T, NT, MT, WC, LY_GATHER_ROWS, LY_PRO_AFFINE_RELU_CA>(P, st);
-  return launch_gemm_v<T, T, NT, MT, WC, LY_GATHER_ROWS, LY_PRO_NONE>(P, st);
+  if (P.pro == LY_PRO_GATE) return launch_gemm_v<T, T, NT, MT, WC, LY_GATHER_ROWS, LY_PRO_GATE>(P, out);
+  if (P.pro == LY_PRO_AFFINE_RELU_CA) return launch_gemm_v<T, T, NT, MT, WC, LY_GATHER_ROWS, LY_PRO_AFFINE_RELU_CA>(P, out);
+  return launch_gemm_v<T, T, NT, MT, WC, LY_GATHER_ROWS, LY_PRO_NONE>(P, out);
 }
 
 // Tile policy, measured on MI355X at every LEAD-YOLO shape: 64-pixel tiles with 3 co-resident blocks per CU beat 128-pixel
 // tiles (one wave per SIMD); the narrow-output tile trades channels for pixels.  (bf16 storage, whole train step: 64 x 64 tiles for
 // N > 64 — four waves per SIMD instead of two — 19.95 vs 19.79 ms: no gain, the 64 x 128 tile stays.)
 template <typename T>
-static int ly_gemm_dispatch(const LyGemmParams& P, hipStream_t st) {
-  if (P.N > 64) return launch_gemm<T, 4, 2, 4>(P, st);    // 64 px x 128 ch per block
-  if (P.N > 32) return launch_gemm<T, 4, 1, 4>(P, st);    // 64 px x 64 ch
+static int ly_gemm_dispatch(const LyGemmParams& P, const LyOut& out) {
+  if (P.N > 64) return launch_gemm<T, 4, 2, 4>(P, out);    // 64 px x 128 ch per block
+  if (P.N > 32) return launch_gemm<T, 4, 1, 4>(P, out);    // 64 px x 64 ch
   // (the CoordAtt-gate prologue on the 128 px x 32 ch tile compiles to 256 registers with 130-320 spilled — tools/kernel_regs.py; lead-yolo-n's
   // 32-channel C3_CA.cv3 takes the 64 x 64 tile with half its channel tiles idle instead)
-  if (P.pro == LY_PRO_GATE) return launch_gemm<T, 4, 1, 4>(P, st);
-  return launch_gemm<T, 2, 2, 1>(P, st);                  // 128 px x 32 ch
+  if (P.pro == LY_PRO_GATE) return launch_gemm<T, 4, 1, 4>(P, out);
+  return launch_gemm<T, 2, 2, 1>(P, out);                  // 128 px x 32 ch
 }
-int ly_gemm_dispatch_f32(const LyGemmParams& P, hipStream_t st);
-int ly_gemm_dispatch_bf16(const LyGemmParams& P, hipStream_t st);
-int ly_patch4_try(const LyGemmParams& P, hipStream_t st);      // ly_patch4.hip: 1 = launched
+int ly_gemm_dispatch_f32(const LyGemmParams& P, const LyOut& out);
+int ly_gemm_dispatch_bf16(const LyGemmParams& P, const LyOut& out);
+int ly_patch4_try(const LyGemmParams& P, const LyOut& out);      // ly_patch4.hip: 1 = launched (or described)

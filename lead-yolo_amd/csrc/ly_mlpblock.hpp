@@ -838,48 +838,54 @@ __global__ __launch_bounds__(LY_THREADS) void ly_mlpblock_pconv1_kernel(const T*
 }
 
 template <typename T, int C, int NT, int HT, bool T2D>
-static int launch_mlp_pconv1(const T* x, T* y, long M, int n_img, int H, int W, const void* wp, hipStream_t st) {
+static int launch_mlp_pconv1(const T* x, T* y, long M, int n_img, int H, int W, const void* wp, const LyOut& out) {
   using Gm = MlpGeom<C>;
   constexpr int BP = 64 * NT;
   const long halo = T2D ? (4 * NT + 2) * 18 : BP + 2 * W + 2;
   size_t lds = LyT<T>::PL * ((size_t)BP * Gm::RS + (size_t)halo * Gm::RSP);
   LY_CHECK(lds <= LY_LDS_MAX, "mlpblock_pconv: tile needs %zu B of LDS (C=%d W=%d)", lds, C, W);
   long blocks = T2D ? (long)n_img * ((H + 4 * NT - 1) / (4 * NT)) * (W / 16) : (M + BP - 1) / BP;
-  return ly_launch_lds<ly_mlpblock_pconv1_kernel<T, C, NT, HT, T2D>>(dim3((unsigned)blocks), dim3(LY_THREADS), lds, st, x, y, M, H, W, reinterpret_cast<const uint4*>(wp));
+  return LY_EMIT(out, (ly_launch_lds<ly_mlpblock_pconv1_kernel<T, C, NT, HT, T2D>>(dim3((unsigned)blocks), dim3(LY_THREADS), lds, out.st, x, y, M, H, W, reinterpret_cast<const uint4*>(wp))),
+                 "ly_mlpblock_pconv1_kernel<%s, %d, %d, %d, %s>", ly_tname<T>(), C, NT, HT, LY_BOOL(T2D));
 }
 
 // The instantiations are split over translation units (ly_mlpblock.hip: C = 16/24/40 + the C ABI, ly_mlpblock_b.hip:
 // C = 80/160, ly_mlpblock_c.hip: C = 320) only to keep the in-tree build short.
 #define LY_MLP_ARGS const void* x, void* y, long M, int n_img, int H, int W, const void* wp, const void* w1, const void* w2, \
-                    const float* s, const float* b, double* stats, int dtype, hipStream_t st
+                    const float* s, const float* b, double* stats, int dtype, const LyOut& out
 int ly_mlp_dispatch_80(LY_MLP_ARGS);
 int ly_mlp_dispatch_160(LY_MLP_ARGS);
 int ly_mlp_dispatch_320(LY_MLP_ARGS);
-int ly_mlp_pconv_80(const void* x, void* y, long M, int n_img, int H, int W, const void* wp, int dtype, hipStream_t st);
-int ly_mlp_pconv_160(const void* x, void* y, long M, int n_img, int H, int W, const void* wp, int dtype, hipStream_t st);
-int ly_mlp_pconv_320(const void* x, void* y, long M, int n_img, int H, int W, const void* wp, int dtype, hipStream_t st);
+int ly_mlp_pconv_80(const void* x, void* y, long M, int n_img, int H, int W, const void* wp, int dtype, const LyOut& out);
+int ly_mlp_pconv_160(const void* x, void* y, long M, int n_img, int H, int W, const void* wp, int dtype, const LyOut& out);
+int ly_mlp_pconv_320(const void* x, void* y, long M, int n_img, int H, int W, const void* wp, int dtype, const LyOut& out);
 
 template <typename T, int C, int NT, int HT, bool T2D, bool STATS, bool RING>
 static int launch_mlp_k(const T* x, T* y, long M, int n_img, int H, int W, const void* wp, const void* w1, const void* w2,
-                        const float* s, const float* b, double* stats, hipStream_t st) {
+                        const float* s, const float* b, double* stats, const LyOut& out) {
   using Gm = MlpGeom<C>;
   constexpr int BP = 64 * NT;
   const long halo = T2D ? (4 * NT + 2) * 18 : BP + 2 * W + 2;
   size_t lds = LyT<T>::PL * ((size_t)BP * Gm::RS + (size_t)halo * Gm::RSP) + (STATS ? 4 * 2 * Gm::HTP * 16 * sizeof(float) : 0);
   LY_CHECK(lds <= LY_LDS_MAX, "mlpblock: tile needs %zu B of LDS (C=%d W=%d)", lds, C, W);
-  constexpr auto k = [] {
-    if constexpr (RING) return ly_mlpblock_fwd_ring_kernel<T, C, NT, HT, T2D, STATS>;
-    else if constexpr (C <= 24 && T2D) return ly_mlpblock_fwd_occ4_kernel<T, C, NT, HT, T2D, STATS>;
-    else return ly_mlpblock_fwd_kernel<T, C, NT, HT, T2D, STATS>;
+  struct Kernel {
+    decltype(&ly_mlpblock_fwd_kernel<T, C, NT, HT, T2D, STATS>) fn;
+    const char* name;
+  };
+  constexpr Kernel k = []() -> Kernel {
+    if constexpr (RING) return {ly_mlpblock_fwd_ring_kernel<T, C, NT, HT, T2D, STATS>, "ly_mlpblock_fwd_ring_kernel"};
+    else if constexpr (C <= 24 && T2D) return {ly_mlpblock_fwd_occ4_kernel<T, C, NT, HT, T2D, STATS>, "ly_mlpblock_fwd_occ4_kernel"};
+    else return {ly_mlpblock_fwd_kernel<T, C, NT, HT, T2D, STATS>, "ly_mlpblock_fwd_kernel"};
   }();
   long blocks = T2D ? (long)n_img * ((H + 4 * NT - 1) / (4 * NT)) * (W / 16) : (M + BP - 1) / BP;
-  return ly_launch_lds<k>(dim3((unsigned)blocks), dim3(LY_THREADS), lds, st, x, y, M, H, W, reinterpret_cast<const uint4*>(wp),
-                          reinterpret_cast<const uint4*>(w1), reinterpret_cast<const uint4*>(w2), s, b, stats);
+  return LY_EMIT(out, (ly_launch_lds<k.fn>(dim3((unsigned)blocks), dim3(LY_THREADS), lds, out.st, x, y, M, H, W, reinterpret_cast<const uint4*>(wp),
+                                           reinterpret_cast<const uint4*>(w1), reinterpret_cast<const uint4*>(w2), s, b, stats)),
+                 "%s<%s, %d, %d, %d, %s, %s>", k.name, ly_tname<T>(), C, NT, HT, LY_BOOL(T2D), LY_BOOL(STATS));
 }
 
 template <typename T, int C, int NT, int HT, int MODE>
 static int launch_mlp_persist(const T* x, T* y, long M, int n_img, int H, int W, const void* wp, const void* w1, const void* w2,
-                              const float* s, const float* b, double* stats, hipStream_t st) {
+                              const float* s, const float* b, double* stats, const LyOut& out) {
   using Gm = MlpGeom<C>;
   constexpr int PL = LyT<T>::PL, BP = 64 * NT, BPH = (4 * NT + 2) * 18;
   constexpr int NFW = Gm::PT * Gm::SP + Gm::HTP * Gm::S1 + Gm::C16 * Gm::S2;
@@ -887,6 +893,7 @@ static int launch_mlp_persist(const T* x, T* y, long M, int n_img, int H, int W,
   static_assert(lds <= LY_LDS_MAX, "persistent MLPBlock: weights + two patch buffers must fit LDS");
   constexpr int PD = LY_MLP_PD;
   constexpr auto k = ly_mlpblock_persist_kernel<T, C, NT, HT, MODE, PD>;
+  LY_DESCRIBED(out, "ly_mlpblock_persist_kernel<%s, %d, %d, %d, %d, %d>", ly_tname<T>(), C, NT, HT, MODE, PD);
   static int per_cu = 0;
   if (per_cu == 0) {
     LY_TRY(ly_lds_allow<k>());
@@ -898,16 +905,16 @@ static int launch_mlp_persist(const T* x, T* y, long M, int n_img, int H, int W,
   const long ntiles = (long)n_img * ((H + 4 * NT - 1) / (4 * NT)) * (W / 16);
   long blocks = 256L * per_cu;
   if (blocks > ntiles) blocks = ntiles;
-  return ly_launch_lds<k>(dim3((unsigned)blocks), dim3(LY_THREADS), lds, st, x, y, M, H, W, n_img, reinterpret_cast<const uint4*>(wp),
+  return ly_launch_lds<k>(dim3((unsigned)blocks), dim3(LY_THREADS), lds, out.st, x, y, M, H, W, n_img, reinterpret_cast<const uint4*>(wp),
                           reinterpret_cast<const uint4*>(w1), reinterpret_cast<const uint4*>(w2), s, b, stats);
 }
 
 template <typename T, int C, int NT, int HT, bool T2D>
 static int launch_mlp(const T* x, T* y, long M, int n_img, int H, int W, const void* wp, const void* w1, const void* w2,
-                      const float* s, const float* b, double* stats, hipStream_t st) {
+                      const float* s, const float* b, double* stats, const LyOut& out) {
   constexpr bool RING = C >= 80;
-  if (stats) return launch_mlp_k<T, C, NT, HT, T2D, true, RING>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, st);
-  return launch_mlp_k<T, C, NT, HT, T2D, false, RING>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, st);
+  if (stats) return launch_mlp_k<T, C, NT, HT, T2D, true, RING>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, out);
+  return launch_mlp_k<T, C, NT, HT, T2D, false, RING>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, out);
 }
 
 // Tiling policy (kernel time at bs=32 / 64):
@@ -919,51 +926,51 @@ static int launch_mlp(const T* x, T* y, long M, int n_img, int H, int W, const v
 //    (C=80 @ 40x40x32: 26.5 -> 20.7 us; C=160 @ 20x20: 22.6 us with one tile at bs=32, 38.4 -> 28.8 us with two at bs=64).
 template <typename T, int C, int HT, int NTMAX>
 static int dispatch_nt_t(const T* x, T* y, long M, int n_img, int H, int W, const void* wp, const void* w1, const void* w2,
-                         const float* s, const float* b, double* stats, hipStream_t st) {
+                         const float* s, const float* b, double* stats, const LyOut& out) {
   constexpr int NT2 = NTMAX >= 2 ? 2 : NTMAX, NT4 = NTMAX >= 4 ? 4 : NTMAX;
   if (C >= 80) {
     // bf16, C = 80: four pixel tiles per wave (a quarter of the fragment stream per pixel; 236 registers, two waves per SIMD) once that
     // still leaves 384 blocks: 40 x 40 x 64 27.6 -> 25.0 us per block of the stage; at 200 blocks (bs = 32) the forward lost 1 %
     if constexpr (NTMAX >= 4 && LyT<T>::BF) {
-      if (M >= 384L * 256) return launch_mlp<T, C, NT4, HT, false>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, st);
+      if (M >= 384L * 256) return launch_mlp<T, C, NT4, HT, false>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, out);
     }
-    if (NTMAX >= 2 && M >= 200L * 128) return launch_mlp<T, C, NT2, HT, false>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, st);
-    return launch_mlp<T, C, 1, HT, false>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, st);
+    if (NTMAX >= 2 && M >= 200L * 128) return launch_mlp<T, C, NT2, HT, false>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, out);
+    return launch_mlp<T, C, 1, HT, false>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, out);
   }
   if constexpr (C < 80) {
     // persistent patch walk with the weights in LDS: enough patches for every resident block to amortise the weight copy
     // (fp32 storage at C = 40 needs 148 KB of LDS and 242 registers: one block per CU, measured 63 -> 79 us — it keeps the one-shot kernel)
     if ((W & 15) == 0 && W >= 32 && (long)n_img * ((H + 7) / 8) * (W / 16) >= 1024 && (LyT<T>::BF || C < 40))
-      return stats ? launch_mlp_persist<T, C, 2, HT, 1>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, st)
-                   : launch_mlp_persist<T, C, 2, HT, 0>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, st);
+      return stats ? launch_mlp_persist<T, C, 2, HT, 1>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, out)
+                   : launch_mlp_persist<T, C, 2, HT, 0>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, out);
   }
-  if ((W & 15) == 0 && W >= 64 && NTMAX >= 2) return launch_mlp<T, C, 2, HT, true>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, st);
-  if (NTMAX >= 4 && M >= 256L * 1024) return launch_mlp<T, C, NT4, HT, false>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, st);
-  if (NTMAX >= 2 && M >= 128L * 512) return launch_mlp<T, C, NT2, HT, false>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, st);
-  return launch_mlp<T, C, 1, HT, false>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, st);
+  if ((W & 15) == 0 && W >= 64 && NTMAX >= 2) return launch_mlp<T, C, 2, HT, true>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, out);
+  if (NTMAX >= 4 && M >= 256L * 1024) return launch_mlp<T, C, NT4, HT, false>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, out);
+  if (NTMAX >= 2 && M >= 128L * 512) return launch_mlp<T, C, NT2, HT, false>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, out);
+  return launch_mlp<T, C, 1, HT, false>(x, y, M, n_img, H, W, wp, w1, w2, s, b, stats, out);
 }
 
 // the partial conv alone (persist MODE 2) where the persistent kernel applies; returns 1 = "not built for this shape" (the caller then
 // uses a clone + ly_conv3x3_fwd)
 template <int C, int HT>
-static int dispatch_pconv(const void* x, void* y, long M, int n_img, int H, int W, const void* wp, int dtype, hipStream_t st) {
+static int dispatch_pconv(const void* x, void* y, long M, int n_img, int H, int W, const void* wp, int dtype, const LyOut& out) {
   if constexpr (C < 80) {
     const bool shape_ok = (W & 15) == 0 && W >= 32 && (long)n_img * ((H + 7) / 8) * (W / 16) >= 1024;
     if (shape_ok && dtype == LY_BF16)
-      return launch_mlp_persist<__bf16, C, 2, HT, 2>(reinterpret_cast<const __bf16*>(x), reinterpret_cast<__bf16*>(y), M, n_img, H, W, wp, wp, wp, nullptr, nullptr, nullptr, st);
+      return launch_mlp_persist<__bf16, C, 2, HT, 2>(reinterpret_cast<const __bf16*>(x), reinterpret_cast<__bf16*>(y), M, n_img, H, W, wp, wp, wp, nullptr, nullptr, nullptr, out);
     if constexpr (C < 40) {
       if (shape_ok && dtype == LY_F32)
-        return launch_mlp_persist<float, C, 2, HT, 2>(reinterpret_cast<const float*>(x), reinterpret_cast<float*>(y), M, n_img, H, W, wp, wp, wp, nullptr, nullptr, nullptr, st);
+        return launch_mlp_persist<float, C, 2, HT, 2>(reinterpret_cast<const float*>(x), reinterpret_cast<float*>(y), M, n_img, H, W, wp, wp, wp, nullptr, nullptr, nullptr, out);
     }
   }
   // any other map: the one-shot kernel on flattened 64-pixel runs, stopped after the partial conv
-  if (dtype == LY_BF16) return launch_mlp_pconv1<__bf16, C, 1, HT, false>(reinterpret_cast<const __bf16*>(x), reinterpret_cast<__bf16*>(y), M, n_img, H, W, wp, st);
-  return launch_mlp_pconv1<float, C, 1, HT, false>(reinterpret_cast<const float*>(x), reinterpret_cast<float*>(y), M, n_img, H, W, wp, st);
+  if (dtype == LY_BF16) return launch_mlp_pconv1<__bf16, C, 1, HT, false>(reinterpret_cast<const __bf16*>(x), reinterpret_cast<__bf16*>(y), M, n_img, H, W, wp, out);
+  return launch_mlp_pconv1<float, C, 1, HT, false>(reinterpret_cast<const float*>(x), reinterpret_cast<float*>(y), M, n_img, H, W, wp, out);
 }
 
 template <int C, int HT, int NTMAX>
 static int dispatch_nt(LY_MLP_ARGS) {
   if (dtype == LY_BF16)
-    return dispatch_nt_t<__bf16, C, HT, NTMAX>(reinterpret_cast<const __bf16*>(x), reinterpret_cast<__bf16*>(y), M, n_img, H, W, wp, w1, w2, s, b, stats, st);
-  return dispatch_nt_t<float, C, HT, NTMAX>(reinterpret_cast<const float*>(x), reinterpret_cast<float*>(y), M, n_img, H, W, wp, w1, w2, s, b, stats, st);
+    return dispatch_nt_t<__bf16, C, HT, NTMAX>(reinterpret_cast<const __bf16*>(x), reinterpret_cast<__bf16*>(y), M, n_img, H, W, wp, w1, w2, s, b, stats, out);
+  return dispatch_nt_t<float, C, HT, NTMAX>(reinterpret_cast<const float*>(x), reinterpret_cast<float*>(y), M, n_img, H, W, wp, w1, w2, s, b, stats, out);
 }

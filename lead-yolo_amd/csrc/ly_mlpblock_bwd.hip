@@ -19,14 +19,14 @@ extern "C" long ly_mlpblock_bwd_slab_floats(int C) {
   }
 }
 
-extern "C" int ly_mlpblock_bwd(const void* x, const void* dy, void* g, int n_img, int H, int W, int C, const void* wp, const void* w1,
-                               const void* w2t, const void* w1t, const float* a, const float* b, const float* alpha, const float* kappa,
-                               const float* lambda, double* stats, float* slab, long slab_floats, float* dw1, float* dw2, int pass, int dtype,
-                               void* stream) {
+// ly_mlpblock_bwd and its description (a shape and the pass, no pointers to check)
+static int mlp_bwd_entry(const void* x, const void* dy, void* g, int n_img, int H, int W, int C, const void* wp, const void* w1, const void* w2t,
+                         const void* w1t, const float* a, const float* b, const float* alpha, const float* kappa, const float* lambda, double* stats,
+                         float* slab, long slab_floats, float* dw1, float* dw2, int pass, int dtype, const LyOut& out) {
   LY_CHECK(dtype == LY_BF16, "mlpblock_bwd: bf16 storage only (dtype %d)", dtype);
   LY_CHECK(pass == 1 || pass == 2, "mlpblock_bwd: pass must be 1 (BatchNorm sums) or 2 (g, weight gradients)");
-  LY_CHECK(x && dy && wp && w1 && w2t && a && b && n_img > 0 && H > 0 && W > 0, "mlpblock_bwd: bad arguments");
-  LY_CHECK(pass == 1 ? stats != nullptr : (g && w1t && alpha && kappa && lambda && slab && dw1 && dw2), "mlpblock_bwd: pass %d misses a pointer", pass);
+  LY_CHECK((out.name || (x && dy && wp && w1 && w2t && a && b)) && n_img > 0 && H > 0 && W > 0, "mlpblock_bwd: bad arguments");
+  if (!out.name) LY_CHECK(pass == 1 ? stats != nullptr : (g && w1t && alpha && kappa && lambda && slab && dw1 && dw2), "mlpblock_bwd: pass %d misses a pointer", pass);
   LY_CHECK(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)g & 15) == 0 && ((uintptr_t)slab & 15) == 0, "mlpblock_bwd: x / dy / g / slab must be 16-byte aligned");
   const long M = (long)n_img * H * W;
   LY_CHECK(M < (1L << 24), "mlpblock_bwd: M=%ld pixels exceeds the 2^24 limit of the fast index path", M);
@@ -36,16 +36,30 @@ extern "C" int ly_mlpblock_bwd(const void* x, const void* dy, void* g, int n_img
   P.wp = reinterpret_cast<const uint4*>(wp); P.w1 = reinterpret_cast<const uint4*>(w1);
   P.w2t = reinterpret_cast<const uint4*>(w2t); P.w1t = reinterpret_cast<const uint4*>(w1t);
   P.a = a; P.b = b; P.alpha = alpha; P.kappa = kappa; P.lambda = lambda; P.stats = stats; P.slab = slab;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   switch (C) {
-    case 16: return mlp_bwd_pass<16, 2>(P, pass, slab_floats, dw1, dw2, st);
-    case 24: return mlp_bwd_pass<24, 2>(P, pass, slab_floats, dw1, dw2, st);
-    case 40: return mlp_bwd_pass<40, 2>(P, pass, slab_floats, dw1, dw2, st);
-    case 80: return ly_mlp_bwd_pass_80(P, pass, slab_floats, dw1, dw2, st);
+    case 16: return mlp_bwd_pass<16, 2>(P, pass, slab_floats, dw1, dw2, out);
+    case 24: return mlp_bwd_pass<24, 2>(P, pass, slab_floats, dw1, dw2, out);
+    case 40: return mlp_bwd_pass<40, 2>(P, pass, slab_floats, dw1, dw2, out);
+    case 80: return ly_mlp_bwd_pass_80(P, pass, slab_floats, dw1, dw2, out);
     default:
       ly_set_error("mlpblock_bwd: unsupported channel count C=%d (built for 16/24/40/80)", C);
       return -1;
   }
+}
+
+extern "C" int ly_mlpblock_bwd(const void* x, const void* dy, void* g, int n_img, int H, int W, int C, const void* wp, const void* w1,
+                               const void* w2t, const void* w1t, const float* a, const float* b, const float* alpha, const float* kappa,
+                               const float* lambda, double* stats, float* slab, long slab_floats, float* dw1, float* dw2, int pass, int dtype,
+                               void* stream) {
+  return mlp_bwd_entry(x, dy, g, n_img, H, W, C, wp, w1, w2t, w1t, a, b, alpha, kappa, lambda, stats, slab, slab_floats, dw1, dw2, pass, dtype,
+                       LY_ON_STREAM(stream));
+}
+
+// the pass kernel (pass 2: not its fold)
+extern "C" int ly_mlpblock_bwd_describe(int n_img, int H, int W, int C, int dtype, int pass, char* name, int cap) {
+  LY_CHECK(name && cap > 0, "mlpblock_bwd_describe: bad arguments");
+  return mlp_bwd_entry(nullptr, nullptr, nullptr, n_img, H, W, C, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                       nullptr, nullptr, pass, dtype, LyOut{nullptr, name, cap});
 }
 
 // 1 when ly_mlpblock_bwd_dx is built for (C, map width W, dtype) and its tile fits the 160 KB of LDS (C = 320 never does: 118 KB of tap fragments
@@ -63,10 +77,10 @@ extern "C" int ly_mlpblock_bwd_dx_ok(int C, int W, int dtype) {
 
 // dx = dy + [pconv^T(g[:, :C/4]) | g[:, C/4:]] and (where built: 2-D patches, C/4 <= 32) dwp += the partial conv's weight gradient, one launch
 // (+ a combine).  Returns 0: both done; 1: dx done, dwp left to the caller (ly_wgrad on g, x); < 0: error.
-extern "C" int ly_mlpblock_bwd_dx(const void* g, const void* dy, const void* x, void* dx, int n_img, int H, int W, int C, const void* wpt, float* slab,
-                                  long slab_floats, float* dwp, int lddw, int dw_ts, int dw_cs, int dtype, void* stream) {
+static int mlp_bwd_dx_entry(const void* g, const void* dy, const void* x, void* dx, int n_img, int H, int W, int C, const void* wpt, float* slab,
+                            long slab_floats, float* dwp, int lddw, int dw_ts, int dw_cs, int dtype, const LyOut& out) {
   LY_CHECK(dtype == LY_BF16, "mlpblock_bwd_dx: bf16 storage only (dtype %d)", dtype);
-  LY_CHECK(g && dy && x && dx && wpt && n_img > 0 && H > 0 && W > 0 && dx != g && dx != dy, "mlpblock_bwd_dx: bad arguments");
+  LY_CHECK((out.name || (g && dy && x && dx && wpt && dx != g && dx != dy)) && n_img > 0 && H > 0 && W > 0, "mlpblock_bwd_dx: bad arguments");
   LY_CHECK(((uintptr_t)g & 15) == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dx & 15) == 0 && ((uintptr_t)slab & 15) == 0,
            "mlpblock_bwd_dx: g / dy / x / dx / slab must be 16-byte aligned");
   const long M = (long)n_img * H * W;
@@ -76,15 +90,26 @@ extern "C" int ly_mlpblock_bwd_dx(const void* g, const void* dy, const void* x, 
   P.dx = reinterpret_cast<__bf16*>(dx); P.M = M; P.H = H; P.W = W; P.n_img = n_img; P.ntiles = 0;
   P.wpt = reinterpret_cast<const uint4*>(wpt); P.slab = slab;
   if (!slab) dwp = nullptr;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   switch (C) {
-    case 16: return dispatch_mlp_bwd_dx<16>(P, slab_floats, dwp, lddw, dw_ts, dw_cs, st);
-    case 24: return dispatch_mlp_bwd_dx<24>(P, slab_floats, dwp, lddw, dw_ts, dw_cs, st);
-    case 40: return dispatch_mlp_bwd_dx<40>(P, slab_floats, dwp, lddw, dw_ts, dw_cs, st);
-    case 80: return ly_mlp_bwd_dx_80(P, slab_floats, dwp, lddw, dw_ts, dw_cs, st);
-    case 160: return ly_mlp_bwd_dx_160(P, slab_floats, dwp, lddw, dw_ts, dw_cs, st);
+    case 16: return dispatch_mlp_bwd_dx<16>(P, slab_floats, dwp, lddw, dw_ts, dw_cs, out);
+    case 24: return dispatch_mlp_bwd_dx<24>(P, slab_floats, dwp, lddw, dw_ts, dw_cs, out);
+    case 40: return dispatch_mlp_bwd_dx<40>(P, slab_floats, dwp, lddw, dw_ts, dw_cs, out);
+    case 80: return ly_mlp_bwd_dx_80(P, slab_floats, dwp, lddw, dw_ts, dw_cs, out);
+    case 160: return ly_mlp_bwd_dx_160(P, slab_floats, dwp, lddw, dw_ts, dw_cs, out);
     default:
       ly_set_error("mlpblock_bwd_dx: unsupported channel count C=%d (built for 16/24/40/80/160)", C);
       return -1;
   }
+}
+
+extern "C" int ly_mlpblock_bwd_dx(const void* g, const void* dy, const void* x, void* dx, int n_img, int H, int W, int C, const void* wpt, float* slab,
+                                  long slab_floats, float* dwp, int lddw, int dw_ts, int dw_cs, int dtype, void* stream) {
+  return mlp_bwd_dx_entry(g, dy, x, dx, n_img, H, W, C, wpt, slab, slab_floats, dwp, lddw, dw_ts, dw_cs, dtype, LY_ON_STREAM(stream));
+}
+
+// with_dw: the call would pass a slab and dwp (the dispatch reads only whether they are null)
+extern "C" int ly_mlpblock_bwd_dx_describe(int n_img, int H, int W, int C, int dtype, int with_dw, char* name, int cap) {
+  LY_CHECK(name && cap > 0, "mlpblock_bwd_dx_describe: bad arguments");
+  float* const given = with_dw ? reinterpret_cast<float*>((uintptr_t)16) : nullptr;
+  return mlp_bwd_dx_entry(nullptr, nullptr, nullptr, nullptr, n_img, H, W, C, nullptr, given, 0, given, 0, 0, 0, dtype, LyOut{nullptr, name, cap});
 }

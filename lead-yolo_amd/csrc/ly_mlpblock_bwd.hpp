@@ -681,7 +681,7 @@ __global__ __launch_bounds__(1024) void ly_mlpblock_bwd_combine_kernel(const flo
 }
 
 template <int C, int HT, bool T2D, int PASS>
-static int launch_mlp_bwd(LyMlpBwdArgs P, long slab_floats, int* blocks_out, hipStream_t st) {
+static int launch_mlp_bwd(LyMlpBwdArgs P, long slab_floats, int* blocks_out, const LyOut& out) {
   constexpr int PD = 1;
   using Gm = MlpGeom<C>;
   using Bg = MlpBwdGeom<C, PASS>;
@@ -691,6 +691,7 @@ static int launch_mlp_bwd(LyMlpBwdArgs P, long slab_floats, int* blocks_out, hip
                      ((size_t)halo * Gm::RSP + 15) / 16 * 16 + (PASS == 2 ? 2 * (size_t)BP * Bg::RSD : 0);
   LY_CHECK(lds <= LY_LDS_MAX, "mlpblock_bwd: tile needs %zu B of LDS (C=%d W=%d)", lds, C, P.W);
   constexpr auto k = ly_mlpblock_bwd_kernel<C, HT, T2D, PASS, PD>;
+  LY_DESCRIBED(out, "ly_mlpblock_bwd_kernel<%d, %d, %s, %d, %d>", C, HT, LY_BOOL(T2D), PASS, PD);
   static int per_cu = 0;
   static size_t lds_q = 0;
   LY_TRY(ly_lds_allow<k>());        // ahead of the occupancy query
@@ -710,7 +711,7 @@ static int launch_mlp_bwd(LyMlpBwdArgs P, long slab_floats, int* blocks_out, hip
              blocks * (long)Bg::SLAB);
   }
   P.ntiles = (int)ntiles;
-  LY_TRY(ly_launch_lds<k>(dim3((unsigned)blocks), dim3(LY_THREADS), lds, st, P));
+  LY_TRY(ly_launch_lds<k>(dim3((unsigned)blocks), dim3(LY_THREADS), lds, out.st, P));
   if (blocks_out) *blocks_out = (int)blocks;
   return 0;
 }
@@ -726,22 +727,22 @@ static int launch_mlp_bwd_combine(const float* slab, int nblk, float* dw1, float
 
 // patches (with the next patch prefetched) unless more than a quarter of the 16-wide patch columns would lie outside the map
 template <int C, int HT, int PASS>
-static int dispatch_mlp_bwd(LyMlpBwdArgs P, long slab_floats, int* blocks_out, hipStream_t st) {
+static int dispatch_mlp_bwd(LyMlpBwdArgs P, long slab_floats, int* blocks_out, const LyOut& out) {
   const int wp16 = (P.W + 15) / 16 * 16;
-  if (P.W >= 12 && 4 * (wp16 - P.W) <= wp16) return launch_mlp_bwd<C, HT, true, PASS>(P, slab_floats, blocks_out, st);
-  return launch_mlp_bwd<C, HT, false, PASS>(P, slab_floats, blocks_out, st);
+  if (P.W >= 12 && 4 * (wp16 - P.W) <= wp16) return launch_mlp_bwd<C, HT, true, PASS>(P, slab_floats, blocks_out, out);
+  return launch_mlp_bwd<C, HT, false, PASS>(P, slab_floats, blocks_out, out);
 }
 
 template <int C, int HT>
-static int mlp_bwd_pass(LyMlpBwdArgs P, int pass, long slab_floats, float* dw1, float* dw2, hipStream_t st) {
-  if (pass == 1) return dispatch_mlp_bwd<C, HT, 1>(P, 0, nullptr, st);
+static int mlp_bwd_pass(LyMlpBwdArgs P, int pass, long slab_floats, float* dw1, float* dw2, const LyOut& out) {
+  if (pass == 1) return dispatch_mlp_bwd<C, HT, 1>(P, 0, nullptr, out);
   int blocks = 0;
-  const int rc = dispatch_mlp_bwd<C, HT, 2>(P, slab_floats, &blocks, st);
-  if (rc) return rc;
-  return launch_mlp_bwd_combine<C>(P.slab, blocks, dw1, dw2, st);
+  const int rc = dispatch_mlp_bwd<C, HT, 2>(P, slab_floats, &blocks, out);
+  if (rc || out.name) return rc;
+  return launch_mlp_bwd_combine<C>(P.slab, blocks, dw1, dw2, out.st);
 }
 
-int ly_mlp_bwd_pass_80(LyMlpBwdArgs P, int pass, long slab_floats, float* dw1, float* dw2, hipStream_t st);
+int ly_mlp_bwd_pass_80(LyMlpBwdArgs P, int pass, long slab_floats, float* dw1, float* dw2, const LyOut& out);
 
 // -------------------------------------------------------------------------------------------------------------------------------------------
 // The tail of the MLPBlock backward in ONE launch (was: partial-conv weight gradient through the generic tiled kernel — 84 us at 160 x 160 x 24,
@@ -1118,12 +1119,13 @@ template <int C>
 static bool mlp_bwd_dx_fits(int W) { return mlp_bwd_dx_lds<C>(mlp_bwd_dx_patches(W), W) <= LY_LDS_MAX; }
 
 template <int C, bool T2D, bool WG>
-static int launch_mlp_bwd_dx(LyMlpDxArgs P, long slab_floats, float* dwp, int lddw, int ts, int cs, hipStream_t st) {
+static int launch_mlp_bwd_dx(LyMlpDxArgs P, long slab_floats, float* dwp, int lddw, int ts, int cs, const LyOut& out) {
   using Gm = MlpGeom<C>;
   constexpr int BP = 128, PT = Gm::PT;
   const size_t lds = mlp_bwd_dx_lds<C>(T2D, P.W);
   LY_CHECK(lds <= LY_LDS_MAX, "mlpblock_bwd_dx: tile needs %zu B of LDS (C=%d W=%d)", lds, C, P.W);
   constexpr auto k = ly_mlpblock_bwd_dx_kernel<C, T2D, WG>;
+  LY_DESCRIBED(out, "ly_mlpblock_bwd_dx_kernel<%d, %s, %s>", C, LY_BOOL(T2D), LY_BOOL(WG));
   static int per_cu = 0;
   static size_t lds_q = 0;
   LY_TRY(ly_lds_allow<k>());        // ahead of the occupancy query
@@ -1141,10 +1143,10 @@ static int launch_mlp_bwd_dx(LyMlpDxArgs P, long slab_floats, float* dwp, int ld
   constexpr int SL = 9 * PT * PT * 256;
   if (WG) LY_CHECK(P.slab && dwp && blocks * (long)SL <= slab_floats, "mlpblock_bwd_dx: the slab workspace holds %ld floats, %ld needed", slab_floats, blocks * (long)SL);
   P.ntiles = (int)ntiles;
-  LY_TRY(ly_launch_lds<k>(dim3((unsigned)blocks), dim3(LY_THREADS), lds, st, P));
+  LY_TRY(ly_launch_lds<k>(dim3((unsigned)blocks), dim3(LY_THREADS), lds, out.st, P));
   if (WG) {
     constexpr int NE = 9 * PT * PT * 64, EL = NE >= 2304 ? 32 : 8;      // 72 blocks in both cases
-    hipLaunchKernelGGL((ly_mlpblock_bwd_dx_combine_kernel<C, EL>), dim3((NE + EL - 1) / EL), dim3(1024), 0, st, P.slab, (int)blocks, dwp, lddw, ts, cs);
+    hipLaunchKernelGGL((ly_mlpblock_bwd_dx_combine_kernel<C, EL>), dim3((NE + EL - 1) / EL), dim3(1024), 0, out.st, P.slab, (int)blocks, dwp, lddw, ts, cs);
   }
   LY_LAUNCH_CHECK();
   return WG ? 0 : 1;
@@ -1152,15 +1154,15 @@ static int launch_mlp_bwd_dx(LyMlpDxArgs P, long slab_floats, float* dwp, int ld
 
 // returns 0: dx and dwp done; 1: dx done, the partial conv's weight gradient is left to the caller (ly_wgrad); < 0: error
 template <int C>
-static int dispatch_mlp_bwd_dx(LyMlpDxArgs P, long slab_floats, float* dwp, int lddw, int ts, int cs, hipStream_t st) {
+static int dispatch_mlp_bwd_dx(LyMlpDxArgs P, long slab_floats, float* dwp, int lddw, int ts, int cs, const LyOut& out) {
   const bool patches = mlp_bwd_dx_patches(P.W);
   if constexpr (MlpGeom<C>::PT <= 2) {
-    if (patches && dwp) return launch_mlp_bwd_dx<C, true, true>(P, slab_floats, dwp, lddw, ts, cs, st);
+    if (patches && dwp) return launch_mlp_bwd_dx<C, true, true>(P, slab_floats, dwp, lddw, ts, cs, out);
   }
-  if (patches) return launch_mlp_bwd_dx<C, true, false>(P, 0, nullptr, 0, 0, 0, st);
-  return launch_mlp_bwd_dx<C, false, false>(P, 0, nullptr, 0, 0, 0, st);
+  if (patches) return launch_mlp_bwd_dx<C, true, false>(P, 0, nullptr, 0, 0, 0, out);
+  return launch_mlp_bwd_dx<C, false, false>(P, 0, nullptr, 0, 0, 0, out);
 }
 
-int ly_mlp_bwd_dx_80(LyMlpDxArgs P, long slab_floats, float* dwp, int lddw, int ts, int cs, hipStream_t st);
-int ly_mlp_bwd_dx_160(LyMlpDxArgs P, long slab_floats, float* dwp, int lddw, int ts, int cs, hipStream_t st);
+int ly_mlp_bwd_dx_80(LyMlpDxArgs P, long slab_floats, float* dwp, int lddw, int ts, int cs, const LyOut& out);
+int ly_mlp_bwd_dx_160(LyMlpDxArgs P, long slab_floats, float* dwp, int lddw, int ts, int cs, const LyOut& out);
 bool ly_mlp_bwd_dx_fits_wide(int C, int W);

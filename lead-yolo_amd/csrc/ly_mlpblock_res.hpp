@@ -386,7 +386,7 @@ __global__ __launch_bounds__(LY_RES_THREADS) void ly_mlpblock_res_kernel(
 // launch: returns 1 when the shape is outside what the kernel is built for (the caller then takes the one-shot kernels)
 template <typename T, int C, int NT, int HT, int D>
 static int launch_mlp_res(const T* x, T* y, long M, int H, int W, const void* wp, const void* w1, const void* w2,
-                          const float* s, const float* b, double* stats, hipStream_t st) {
+                          const float* s, const float* b, double* stats, const LyOut& out) {
   using Gm = MlpGeom<C>;
   constexpr int BP = LY_RES_WAVES * 16 * NT;
   constexpr int NFW = Gm::PT * Gm::SP + Gm::HTP * Gm::S1 + Gm::C16 * Gm::S2;
@@ -400,10 +400,11 @@ static int launch_mlp_res(const T* x, T* y, long M, int H, int W, const void* wp
   if (blocks > 256) blocks = 256;
   long per_block = ((M + blocks - 1) / blocks + 15) / 16 * 16;
   blocks = (M + per_block - 1) / per_block;
-#define LY_RES_LAUNCH(STATS_)                                                                                                                  \
-  ly_launch_lds<ly_mlpblock_res_kernel<T, C, NT, HT, STATS_, D>>(dim3((unsigned)blocks), dim3(LY_RES_THREADS), lds, st, x, y, M, H, W, (int)per_block, \
-                                                                 reinterpret_cast<const uint4*>(wp), reinterpret_cast<const uint4*>(w1),       \
-                                                                 reinterpret_cast<const uint4*>(w2), s, b, stats)
+#define LY_RES_LAUNCH(STATS_)                                                                                                                              \
+  LY_EMIT(out, (ly_launch_lds<ly_mlpblock_res_kernel<T, C, NT, HT, STATS_, D>>(dim3((unsigned)blocks), dim3(LY_RES_THREADS), lds, out.st, x, y, M, H, W, (int)per_block, \
+                                                                               reinterpret_cast<const uint4*>(wp), reinterpret_cast<const uint4*>(w1),     \
+                                                                               reinterpret_cast<const uint4*>(w2), s, b, stats)),                          \
+          "ly_mlpblock_res_kernel<%s, %d, %d, %d, " #STATS_ ", %d>", ly_tname<T>(), C, NT, HT, D)
   return stats ? LY_RES_LAUNCH(true) : LY_RES_LAUNCH(false);
 #undef LY_RES_LAUNCH
 }

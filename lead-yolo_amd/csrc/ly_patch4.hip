@@ -153,38 +153,41 @@ __global__ __launch_bounds__(LY_THREADS) void ly_patch4_kernel(const LyGemmParam
 }
 
 template <typename TI, typename TO, int MT>
-static void patch4_launch_mt(const LyGemmParams& P, int ntiles, float in_scale, hipStream_t st) {
+static int patch4_launch_mt(const LyGemmParams& P, int ntiles, float in_scale, const LyOut& out) {
   // a wave walks ~2 U-groups at least; 8 blocks of four waves per CU at most
   long blocks = ((long)ntiles + 4 * LY_P4_U * 2 - 1) / (4 * LY_P4_U * 2);
   blocks = blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks;
-  if (P.stats) hipLaunchKernelGGL((ly_patch4_kernel<TI, TO, MT, true>), dim3((unsigned)blocks), dim3(LY_THREADS), 0, st, P, ntiles, in_scale);
-  else hipLaunchKernelGGL((ly_patch4_kernel<TI, TO, MT, false>), dim3((unsigned)blocks), dim3(LY_THREADS), 0, st, P, ntiles, in_scale);
+#define P4(STATS_)                                                                                                                                   \
+  LY_EMIT(out, (ly_launch<ly_patch4_kernel<TI, TO, MT, STATS_>>(dim3((unsigned)blocks), dim3(LY_THREADS), 0, out.st, P, ntiles, in_scale)), \
+          "ly_patch4_kernel<%s, %s, %d, " #STATS_ ">", ly_tname<TI>(), ly_tname<TO>(), MT)
+  return P.stats ? P4(true) : P4(false);
+#undef P4
 }
 
 template <typename TI, typename TO>
-static void patch4_launch(const LyGemmParams& P, float in_scale, hipStream_t st) {
+static int patch4_launch(const LyGemmParams& P, float in_scale, const LyOut& out) {
   const int ntiles = (int)((P.M + 15) / 16);
   const int mt = (P.N + 15) / 16;
-  if (mt <= 2) patch4_launch_mt<TI, TO, 2>(P, ntiles, in_scale, st);
-  else if (mt == 3) patch4_launch_mt<TI, TO, 3>(P, ntiles, in_scale, st);
-  else if (mt == 4) patch4_launch_mt<TI, TO, 4>(P, ntiles, in_scale, st);
-  else patch4_launch_mt<TI, TO, 5>(P, ntiles, in_scale, st);
+  if (mt <= 2) return patch4_launch_mt<TI, TO, 2>(P, ntiles, in_scale, out);
+  if (mt == 3) return patch4_launch_mt<TI, TO, 3>(P, ntiles, in_scale, out);
+  if (mt == 4) return patch4_launch_mt<TI, TO, 4>(P, ntiles, in_scale, out);
+  return patch4_launch_mt<TI, TO, 5>(P, ntiles, in_scale, out);
 }
 
-// 1 = launched; 0 = not this kernel's shape (the caller goes on to the generic contraction)
-int ly_patch4_try(const LyGemmParams& P, hipStream_t st) {
+// 1 = launched (or described); 0 = not this kernel's shape (the caller goes on to the generic contraction); < 0: the launch failed
+int ly_patch4_try(const LyGemmParams& P, const LyOut& out) {
   const bool image = P.gather == LY_GATHER_PATCH_NCHW || P.gather == LY_GATHER_PATCH_NCHW_U8 || P.gather == LY_GATHER_PATCH_NCHW_BF16 ||
                      P.gather == LY_GATHER_PATCH_NCHW_F16;
   if (!image || P.Cin != 3 || P.K != 48 || P.N > 80 || P.N < 20 || (P.N & 3) != 0 || (P.out && (P.ldo & 3) != 0) || P.pro != LY_PRO_NONE || P.rowscale || P.res) return 0;
   if (P.Hin != 4 * P.H || P.Win != 4 * P.W) return 0;
   if (P.dtype == LY_BF16) {
-    if (P.gather == LY_GATHER_PATCH_NCHW) patch4_launch<float, __bf16>(P, 1.f, st);
-    else if (P.gather == LY_GATHER_PATCH_NCHW_U8) patch4_launch<unsigned char, __bf16>(P, 1.f / 255.f, st);
-    else if (P.gather == LY_GATHER_PATCH_NCHW_BF16) patch4_launch<ly_bf16img, __bf16>(P, 1.f, st);
-    else patch4_launch<ly_f16img, __bf16>(P, 1.f, st);
+    if (P.gather == LY_GATHER_PATCH_NCHW) LY_TRY(patch4_launch<float, __bf16>(P, 1.f, out));
+    else if (P.gather == LY_GATHER_PATCH_NCHW_U8) LY_TRY(patch4_launch<unsigned char, __bf16>(P, 1.f / 255.f, out));
+    else if (P.gather == LY_GATHER_PATCH_NCHW_BF16) LY_TRY(patch4_launch<ly_bf16img, __bf16>(P, 1.f, out));
+    else LY_TRY(patch4_launch<ly_f16img, __bf16>(P, 1.f, out));
   } else {
-    if (P.gather == LY_GATHER_PATCH_NCHW) patch4_launch<float, float>(P, 1.f, st);
-    else if (P.gather == LY_GATHER_PATCH_NCHW_U8) patch4_launch<unsigned char, float>(P, 1.f / 255.f, st);
+    if (P.gather == LY_GATHER_PATCH_NCHW) LY_TRY(patch4_launch<float, float>(P, 1.f, out));
+    else if (P.gather == LY_GATHER_PATCH_NCHW_U8) LY_TRY(patch4_launch<unsigned char, float>(P, 1.f / 255.f, out));
     else return 0;
   }
   return 1;
@@ -327,8 +330,8 @@ __global__ __launch_bounds__(LY_THREADS) void ly_patch4_wgrad_u8_kernel(const un
   }
 }
 
-extern "C" int ly_patch4_wgrad_u8(const unsigned char* img, int n_img, int C, int H, int W, const void* du, int lddu, int N, float scale, float* slab,
-                                  long slab_floats, float* dw, int dtype, void* stream) {
+static int patch4_wgrad_u8_entry(const unsigned char* img, int n_img, int C, int H, int W, const void* du, int lddu, int N, float scale, float* slab,
+                                 long slab_floats, float* dw, int dtype, const LyOut& out) {
   LY_CHECK(img && du && slab && dw && n_img > 0 && H > 0 && W > 0, "patch4_wgrad_u8: bad arguments");
   LY_CHECK(C == 3 && (H & 3) == 0 && (W & 3) == 0, "patch4_wgrad_u8: built for RGB images with H, W multiples of 4 (C=%d H=%d W=%d)", C, H, W);
   LY_CHECK(dtype == LY_BF16, "patch4_wgrad_u8: bf16 gradients only (fp32 storage keeps ly_patch4_rows_u8 + ly_wgrad)");
@@ -339,13 +342,25 @@ extern "C" int ly_patch4_wgrad_u8(const unsigned char* img, int n_img, int C, in
   const long units = (M + LY_P4W_PX - 1) / LY_P4W_PX;
   long blocks = units < 1536 ? units : 1536;                   // six 22-24 KB blocks per CU
   LY_CHECK(blocks * N * 48 <= slab_floats, "patch4_wgrad_u8: the slab holds %ld floats, %ld needed", slab_floats, blocks * N * 48);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const __bf16* d = reinterpret_cast<const __bf16*>(du);
   const int mtn = (N + 15) / 16;
-  if (mtn == 1) hipLaunchKernelGGL((ly_patch4_wgrad_u8_kernel<1>), dim3((unsigned)blocks), dim3(LY_THREADS), 0, st, img, H, W, M, d, lddu, N, scale, slab);
-  else if (mtn == 2) hipLaunchKernelGGL((ly_patch4_wgrad_u8_kernel<2>), dim3((unsigned)blocks), dim3(LY_THREADS), 0, st, img, H, W, M, d, lddu, N, scale, slab);
-  else if (mtn == 3) hipLaunchKernelGGL((ly_patch4_wgrad_u8_kernel<3>), dim3((unsigned)blocks), dim3(LY_THREADS), 0, st, img, H, W, M, d, lddu, N, scale, slab);
-  else hipLaunchKernelGGL((ly_patch4_wgrad_u8_kernel<4>), dim3((unsigned)blocks), dim3(LY_THREADS), 0, st, img, H, W, M, d, lddu, N, scale, slab);
-  LY_LAUNCH_CHECK();
-  return ly_sum_rows(slab, blocks, (long)N * 48, (long)N * 48, dw, 1, stream);
+#define P4W(MTN_)                                                                                                                                          \
+  LY_EMIT(out, (ly_launch<ly_patch4_wgrad_u8_kernel<MTN_>>(dim3((unsigned)blocks), dim3(LY_THREADS), 0, out.st, img, H, W, M, d, lddu, N, scale, slab)), \
+          "ly_patch4_wgrad_u8_kernel<" #MTN_ ">")
+  LY_TRY(mtn == 1 ? P4W(1) : mtn == 2 ? P4W(2) : mtn == 3 ? P4W(3) : P4W(4));
+#undef P4W
+  if (out.name) return 0;
+  return ly_sum_rows(slab, blocks, (long)N * 48, (long)N * 48, dw, 1, out.st);
+}
+
+extern "C" int ly_patch4_wgrad_u8(const unsigned char* img, int n_img, int C, int H, int W, const void* du, int lddu, int N, float scale, float* slab,
+                                  long slab_floats, float* dw, int dtype, void* stream) {
+  return patch4_wgrad_u8_entry(img, n_img, C, H, W, du, lddu, N, scale, slab, slab_floats, dw, dtype, LY_ON_STREAM(stream));
+}
+
+// the arguments of ly_patch4_wgrad_u8 with (name, cap) for the stream
+extern "C" int ly_patch4_wgrad_u8_describe(const unsigned char* img, int n_img, int C, int H, int W, const void* du, int lddu, int N, float scale, float* slab,
+                                           long slab_floats, float* dw, int dtype, char* name, int cap) {
+  LY_CHECK(name && cap > 0, "patch4_wgrad_u8_describe: bad arguments");
+  return patch4_wgrad_u8_entry(img, n_img, C, H, W, du, lddu, N, scale, slab, slab_floats, dw, dtype, LyOut{nullptr, name, cap});
 }

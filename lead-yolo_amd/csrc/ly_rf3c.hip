@@ -414,7 +414,7 @@ __global__ __launch_bounds__(NW * 64) void ly_rf3c_fwd_kernel(const LyRfcbam3Par
 }
 
 template <typename T, int MT, int NW, int S, bool RAW>
-static int rc_launch_fwd_s(const LyRfcbam3Params& P, const float* wq, hipStream_t st) {
+static int rc_launch_fwd_s(const LyRfcbam3Params& P, const float* wq, const LyOut& out) {
   const int nct = (P.Wo + P.TW - 1) / P.TW, nrt = (P.Ho + P.TH - 1) / P.TH;
   const int gy = (P.N + 16 * NW * MT - 1) / (16 * NW * MT);
   const int IH = P.s * (P.TH - 1) + 3, IW = P.s * (P.TW - 1) + 3;
@@ -422,29 +422,30 @@ static int rc_launch_fwd_s(const LyRfcbam3Params& P, const float* wq, hipStream_
   LY_CHECK(lds <= LY_LDS_MAX, "rf3c_fwd: tile needs %zu B LDS", lds);
   const long nb = (long)P.n_img * nrt * nct * gy;
   LY_CHECK(nb < (1L << 31), "rf3c_fwd: grid too large");
-  return ly_launch_lds<ly_rf3c_fwd_kernel<T, MT, NW, S, RAW>>(dim3((unsigned)nb), dim3(NW * 64), lds, st, P, wq, gy, nct, nrt);
+  return LY_EMIT(out, (ly_launch_lds<ly_rf3c_fwd_kernel<T, MT, NW, S, RAW>>(dim3((unsigned)nb), dim3(NW * 64), lds, out.st, P, wq, gy, nct, nrt)),
+                 "ly_rf3c_fwd_kernel<%s, %d, %d, %d, %s>", ly_tname<T>(), MT, NW, S, LY_BOOL(RAW));
 }
 
 template <typename T, int MT, int NW>
-static int rc_launch_fwd(const LyRfcbam3Params& P, const float* wq, bool raw, hipStream_t st) {
-  if (raw) return P.s == 1 ? rc_launch_fwd_s<T, MT, NW, 1, true>(P, wq, st) : rc_launch_fwd_s<T, MT, NW, 2, true>(P, wq, st);
-  return P.s == 1 ? rc_launch_fwd_s<T, MT, NW, 1, false>(P, wq, st) : rc_launch_fwd_s<T, MT, NW, 2, false>(P, wq, st);
+static int rc_launch_fwd(const LyRfcbam3Params& P, const float* wq, bool raw, const LyOut& out) {
+  if (raw) return P.s == 1 ? rc_launch_fwd_s<T, MT, NW, 1, true>(P, wq, out) : rc_launch_fwd_s<T, MT, NW, 2, true>(P, wq, out);
+  return P.s == 1 ? rc_launch_fwd_s<T, MT, NW, 1, false>(P, wq, out) : rc_launch_fwd_s<T, MT, NW, 2, false>(P, wq, out);
 }
 
 template <typename T>
-static int rc_dispatch_fwd(const LyRfcbam3Params& P, const float* wq, bool raw, hipStream_t st) {
+static int rc_dispatch_fwd(const LyRfcbam3Params& P, const float* wq, bool raw, const LyOut& out) {
   // N <= 128: 4 waves x (MT x 16) output channels, two blocks per CU (bf16); wider: 8 waves share ONE regenerated tile (the VALU phase is
   // split over 16 pixel streams, the contraction over 8 x 32 output channels) instead of regenerating it per 128-channel group
   if constexpr (LyT<T>::BF) {
-    if (P.N > 128) return rc_launch_fwd<T, 2, 8>(P, wq, raw, st);
+    if (P.N > 128) return rc_launch_fwd<T, 2, 8>(P, wq, raw, out);
   }
-  if (P.N > 64) return rc_launch_fwd<T, 2, 4>(P, wq, raw, st);
-  return rc_launch_fwd<T, 1, 4>(P, wq, raw, st);
+  if (P.N > 64) return rc_launch_fwd<T, 2, 4>(P, wq, raw, out);
+  return rc_launch_fwd<T, 1, 4>(P, wq, raw, out);
 }
 
 // P as for ly_rfcbam3_fwd with two differences: P.wg is ignored (wq = the lane-order generate weights, raw != 0: the training form, see
 // ly_rf3c.hpp) and P.wp = conv.0.weight frag-packed as [N][C/32 chunks][9 taps][32 channels] (K = 9*C, no padding).
-extern "C" int ly_rf3c_fwd(const LyRfcbam3Params* p, const float* wq, int raw, void* stream) {
+static int rc_fwd_entry(const LyRfcbam3Params* p, const float* wq, int raw, const LyOut& out) {
   LY_CHECK(p && wq, "rf3c_fwd: null params");
   const LyRfcbam3Params& P = *p;
   LY_CHECK_DTYPE(P.dtype, "rf3c_fwd");
@@ -452,6 +453,12 @@ extern "C" int ly_rf3c_fwd(const LyRfcbam3Params* p, const float* wq, int raw, v
   if (rc_check_tile("rf3c_fwd", P.C, P.s, P.TH, P.TW, P.ldx, P.x)) return -1;
   LY_CHECK((long)P.n_img * P.H * P.W * P.ldx < (1L << 31), "rf3c_fwd: input exceeds the 31-bit offsets of the staging plan");
   LY_CHECK(P.Ho == (P.H + 2 - 3) / P.s + 1 && P.Wo == (P.W + 2 - 3) / P.s + 1, "rf3c_fwd: inconsistent output size");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return P.dtype == LY_BF16 ? rc_dispatch_fwd<__bf16>(P, wq, raw != 0, st) : rc_dispatch_fwd<float>(P, wq, raw != 0, st);
+  return P.dtype == LY_BF16 ? rc_dispatch_fwd<__bf16>(P, wq, raw != 0, out) : rc_dispatch_fwd<float>(P, wq, raw != 0, out);
+}
+
+extern "C" int ly_rf3c_fwd(const LyRfcbam3Params* p, const float* wq, int raw, void* stream) { return rc_fwd_entry(p, wq, raw, LY_ON_STREAM(stream)); }
+
+extern "C" int ly_rf3c_fwd_describe(const LyRfcbam3Params* p, const float* wq, int raw, char* name, int cap) {
+  LY_CHECK(name && cap > 0, "rf3c_fwd_describe: bad arguments");
+  return rc_fwd_entry(p, wq, raw, LyOut{nullptr, name, cap});
 }

@@ -526,13 +526,25 @@ __global__ __launch_bounds__(LY_THREADS) void ly_rf3c_bwd_kernel(const LyRf3cBwd
   }
 }
 
+// LDS bytes of one pass (RB_A / RB_B / RB_C) on TH x TW tiles of a map Wo wide with O output channels: what rb_launch checks against the CU
+// and what the host's tile search (ops.pick_tile_bwd_dx) asks through ly_rf3c_bwd_lds
+static size_t rb_lds(int pass, int TH, int TW, int Wo, int O) {
+  const int nct = (Wo + TW - 1) / TW;
+  const int IH = 2 * (TH - 1) + 3, IW = 2 * (TW - 1) + 3;
+  size_t lds = (size_t)IH * IW * RC_CB * 4 + RC_KR * 128 + RC_TP * (2 * O + 16) + (size_t)32 * 9 * (pass == RB_A ? 2 : 8) * 4 + 64 * 4;
+  if (pass == RB_C) lds += ((size_t)IH * IW + IH + 2 * TW * nct + 2 + 27) * RC_CB * 4;
+  return lds;
+}
+extern "C" int ly_rf3c_bwd_lds(int pass, int TH, int TW, int Wo, int O) {
+  LY_CHECK(pass >= RB_A && pass <= RB_C && TH >= 1 && TW >= 1 && TH * TW <= RC_TP && Wo >= 1 && O >= 1 && O <= 4096, "rf3c_bwd_lds: bad arguments");
+  return (int)rb_lds(pass, TH, TW, Wo, O);
+}
+
 template <int MODE, int KS>
 static int rb_launch(const LyRf3cBwdParams& P, hipStream_t st) {
   const int nct = (P.Wo + P.TW - 1) / P.TW, nrt = (P.Ho + P.TH - 1) / P.TH;
-  const int IH = 2 * (P.TH - 1) + 3, IW = 2 * (P.TW - 1) + 3;
   constexpr int O = 32 * KS;
-  size_t lds = (size_t)IH * IW * RC_CB * 4 + RC_KR * 128 + RC_TP * (2 * O + 16) + (size_t)32 * 9 * (MODE == RB_A ? 2 : 8) * 4 + 64 * 4;
-  if (MODE == RB_C) lds += ((size_t)IH * IW + IH + 2 * P.TW * nct + 2 + 27) * RC_CB * 4;
+  const size_t lds = rb_lds(MODE, P.TH, P.TW, P.Wo, O);
   LY_CHECK(lds <= LY_LDS_MAX, "rf3c_bwd: pass %d needs %zu B LDS for this shape (tile %dx%d, W = %d, O = %d)", MODE, lds, P.TH, P.TW, P.W, O);
   // (launched with the whole LDS of a CU: a block of this family must not share its CU with any other block, see ly_rf3c.hip)
   return ly_launch_lds<ly_rf3c_bwd_kernel<MODE, KS>>(dim3((unsigned)(P.n_img * (P.C / RC_CB))), dim3(LY_THREADS), LY_LDS_MAX, st, P, nct, nrt);

@@ -387,7 +387,7 @@ static int rm_check(const char* who, int C, int s, int TH, int TW, int ldx, cons
 }
 
 template <int MT>
-static int rm_launch_fwd(const LyRfcbam3Params& P, hipStream_t st) {
+static int rm_launch_fwd(const LyRfcbam3Params& P, const LyOut& out) {
   const int nct = (P.Wo + P.TW - 1) / P.TW, nrt = (P.Ho + P.TH - 1) / P.TH;
   const int gy = P.N / (32 * MT);
   const int lds_x = (int)((RM_XTILE + (size_t)P.C * 4 + 63) / 64 * 64);
@@ -401,16 +401,16 @@ static int rm_launch_fwd(const LyRfcbam3Params& P, hipStream_t st) {
 #ifdef LY_RM_DEVEL
   static const int dbg = getenv("LY_RM_DBG") ? atoi(getenv("LY_RM_DBG")) : 0;          // development: 1 = no weight copies (wrong results, timing only)
   static const bool prof = getenv("LY_RM_PROF") != nullptr;
-  if (prof) return ly_launch_lds<ly_rf3m_fwd_kernel<MT, true>>(dim3((unsigned)nb), dim3(RM_THREADS), lds, st, P, nct, nrt, gy, lds_x, dbg);
+  if (prof) return LY_EMIT(out, (ly_launch_lds<ly_rf3m_fwd_kernel<MT, true>>(dim3((unsigned)nb), dim3(RM_THREADS), lds, out.st, P, nct, nrt, gy, lds_x, dbg)), "ly_rf3m_fwd_kernel<%d, true>", MT);
 #else
   const int dbg = 0;
 #endif
-  return ly_launch_lds<ly_rf3m_fwd_kernel<MT, false>>(dim3((unsigned)nb), dim3(RM_THREADS), lds, st, P, nct, nrt, gy, lds_x, dbg);
+  return LY_EMIT(out, (ly_launch_lds<ly_rf3m_fwd_kernel<MT, false>>(dim3((unsigned)nb), dim3(RM_THREADS), lds, out.st, P, nct, nrt, gy, lds_x, dbg)), "ly_rf3m_fwd_kernel<%d, false>", MT);
 }
 
 // P as for ly_rfcbam3_fwd with: dtype LY_BF16, stats == NULL, linear == 0 (inference form), P.wg ignored, TH*TW <= 32, and
 // P.wp = the weight stream of pack.rf3m_stream (N % 64 == 0: blocks of 128 output channels, or 64 when N % 128 != 0)
-extern "C" int ly_rf3m_fwd(const LyRfcbam3Params* p, void* stream) {
+static int rm_fwd_entry(const LyRfcbam3Params* p, const LyOut& out) {
   LY_CHECK(p, "rf3m_fwd: null params");
   const LyRfcbam3Params& P = *p;
   LY_CHECK(P.dtype == LY_BF16, "rf3m_fwd: bf16 storage only (dtype %d)", P.dtype);
@@ -419,9 +419,16 @@ extern "C" int ly_rf3m_fwd(const LyRfcbam3Params* p, void* stream) {
   LY_CHECK(P.N > 0 && (P.N % 64) == 0 && (P.ldo & 7) == 0 && ((uintptr_t)P.out & 15) == 0, "rf3m_fwd: N=%d must be a multiple of 64 (out 16-byte aligned, ldo a multiple of 8)", P.N);
   LY_CHECK((long)P.n_img * P.H * P.W * P.ldx < (1L << 31), "rf3m_fwd: input exceeds the 31-bit offsets of the staging plan");
   LY_CHECK(P.Ho == (P.H + 2 - 3) / P.s + 1 && P.Wo == (P.W + 2 - 3) / P.s + 1, "rf3m_fwd: inconsistent output size");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return (P.N % 128) == 0 ? rm_launch_fwd<4>(P, st) : rm_launch_fwd<2>(P, st);
+  return (P.N % 128) == 0 ? rm_launch_fwd<4>(P, out) : rm_launch_fwd<2>(P, out);
 }
+
+extern "C" int ly_rf3m_fwd(const LyRfcbam3Params* p, void* stream) { return rm_fwd_entry(p, LY_ON_STREAM(stream)); }
+
+extern "C" int ly_rf3m_fwd_describe(const LyRfcbam3Params* p, char* name, int cap) {
+  LY_CHECK(name && cap > 0, "rf3m_fwd_describe: bad arguments");
+  return rm_fwd_entry(p, LyOut{nullptr, name, cap});
+}
+
 
 // ---------------------------------------------------------------------------------------------------
 // statistics pass: mm[n, 3oy + t/3, 3ox + t%3] = [max_c, mean_c] of G, and the SE pooling partials part[n][tile][C] (the sum of the tile's OWN

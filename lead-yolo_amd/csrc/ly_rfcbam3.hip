@@ -279,7 +279,7 @@ __global__ __launch_bounds__(LY_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 }
 
 template <typename T, int MT, bool SW>
-static int launch_rf3_k(const LyRfcbam3Params& P, hipStream_t st) {
+static int launch_rf3_k(const LyRfcbam3Params& P, const LyOut& out) {
   const int nct = (P.Wo + P.TW - 1) / P.TW, nrt = (P.Ho + P.TH - 1) / P.TH;
   const int gy = (P.N + 64 * MT - 1) / (64 * MT);
   const int IH = P.s * (P.TH - 1) + 3, IW = P.s * (P.TW - 1) + 3;
@@ -288,32 +288,36 @@ static int launch_rf3_k(const LyRfcbam3Params& P, hipStream_t st) {
   LY_CHECK(IH * IW * (LY_GCC / 4) <= LY_RF3_NV * LY_THREADS, "rfcbam3: input tile %dx%d exceeds the staging capacity", IH, IW);
   long nb = (long)P.n_img * nrt * nct * gy;
   LY_CHECK(nb < (1L << 31), "rfcbam3: grid too large");
-  if constexpr (SW) return ly_launch_lds<ly_rfcbam3_sw_kernel<T, MT>>(dim3((unsigned)nb), dim3(LY_THREADS), lds, st, P, gy, nct, nrt);
-  else return ly_launch_lds<ly_rfcbam3_kernel<T, MT>>(dim3((unsigned)nb), dim3(LY_THREADS), lds, st, P, gy, nct, nrt);
+  if constexpr (SW)
+    return LY_EMIT(out, (ly_launch_lds<ly_rfcbam3_sw_kernel<T, MT>>(dim3((unsigned)nb), dim3(LY_THREADS), lds, out.st, P, gy, nct, nrt)), "ly_rfcbam3_sw_kernel<%s, %d>",
+                   ly_tname<T>(), MT);
+  else
+    return LY_EMIT(out, (ly_launch_lds<ly_rfcbam3_kernel<T, MT>>(dim3((unsigned)nb), dim3(LY_THREADS), lds, out.st, P, gy, nct, nrt)), "ly_rfcbam3_kernel<%s, %d>",
+                   ly_tname<T>(), MT);
 }
 
 template <typename T, int MT>
-static int launch_rf3(const LyRfcbam3Params& P, hipStream_t st) {
+static int launch_rf3(const LyRfcbam3Params& P, const LyOut& out) {
   const long nb = (long)P.n_img * ((P.Wo + P.TW - 1) / P.TW) * ((P.Ho + P.TH - 1) / P.TH) * ((P.N + 64 * MT - 1) / (64 * MT));
   // Measured: at equal occupancy the LDS path for the generate weights is never slower (128->128 @ 80x80x64: 347 vs 387 us).  The
   // scalar path's one advantage is registers: the MT=4 tile fits two waves per SIMD only with it (245 vs 316), which pays
   // once the grid has more than one block per CU (256->256 @ 40x40x64: 244 vs 292 us; at x32, 224 blocks: 180 vs 156 us).
   if constexpr (MT == 4) {
-    if (nb > 256) return launch_rf3_k<T, MT, true>(P, st);
+    if (nb > 256) return launch_rf3_k<T, MT, true>(P, out);
   }
-  return launch_rf3_k<T, MT, false>(P, st);
+  return launch_rf3_k<T, MT, false>(P, out);
 }
 
 // N > 128 runs as ONE 256-channel tile (MT = 4): with the loads prefetched the regenerate phase is what the kernel waits for, and
 // the wide tile runs it once per pixel tile instead of twice (256->256 @ 40x40x32: module 191 -> 159 us)
 template <typename T>
-static int rf3_dispatch(const LyRfcbam3Params& P, hipStream_t st) {
-  if (P.N > 128) return launch_rf3<T, 4>(P, st);
-  if (P.N > 64) return launch_rf3<T, 2>(P, st);
-  return launch_rf3<T, 1>(P, st);
+static int rf3_dispatch(const LyRfcbam3Params& P, const LyOut& out) {
+  if (P.N > 128) return launch_rf3<T, 4>(P, out);
+  if (P.N > 64) return launch_rf3<T, 2>(P, out);
+  return launch_rf3<T, 1>(P, out);
 }
 
-extern "C" int ly_rfcbam3_fwd(const LyRfcbam3Params* p, void* stream) {
+static int rf3_entry(const LyRfcbam3Params* p, const LyOut& out) {
   LY_CHECK(p, "rfcbam3: null params");
   const LyRfcbam3Params& P = *p;
   LY_CHECK(P.dtype == LY_F32 || P.dtype == LY_BF16, "rfcbam3: unknown dtype %d", P.dtype);
@@ -322,6 +326,12 @@ extern "C" int ly_rfcbam3_fwd(const LyRfcbam3Params* p, void* stream) {
   LY_CHECK(P.s >= 1 && P.TH >= 1 && P.TW >= 1 && P.TH * P.TW <= 64, "rfcbam3: bad tile %dx%d", P.TH, P.TW);
   LY_CHECK((long)P.n_img * P.H * P.W * P.ldx < (1L << 31), "rfcbam3: input of %ld elements exceeds the 31-bit offsets of the staging plan", (long)P.n_img * P.H * P.W * P.ldx);
   LY_CHECK(P.Ho == (P.H + 2 - 3) / P.s + 1 && P.Wo == (P.W + 2 - 3) / P.s + 1, "rfcbam3: inconsistent output size");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return P.dtype == LY_BF16 ? rf3_dispatch<__bf16>(P, st) : rf3_dispatch<float>(P, st);
+  return P.dtype == LY_BF16 ? rf3_dispatch<__bf16>(P, out) : rf3_dispatch<float>(P, out);
+}
+
+extern "C" int ly_rfcbam3_fwd(const LyRfcbam3Params* p, void* stream) { return rf3_entry(p, LY_ON_STREAM(stream)); }
+
+extern "C" int ly_rfcbam3_describe(const LyRfcbam3Params* p, char* name, int cap) {
+  LY_CHECK(name && cap > 0, "rfcbam3_describe: bad arguments");
+  return rf3_entry(p, LyOut{nullptr, name, cap});
 }

@@ -676,34 +676,48 @@ extern "C" int ly_rf_bwd_gen(const void* x, int ldx, int n_img, int H, int W, in
   return 0;
 }
 
-extern "C" int ly_rf_bwd_dx(int n_img, int H, int W, int C, int k, int s, const void* dug, const float* wg, void* dx, int lddx, const float* addnc,
-                            float add_scale, int dtype, void* stream) {
+static int rf_bwd_dx_entry(int n_img, int H, int W, int C, int k, int s, const void* dug, const float* wg, void* dx, int lddx, const float* addnc,
+                           float add_scale, int dtype, const LyOut& out) {
   RF_ARGS_OK(k, C);
   LY_CHECK_DTYPE(dtype, "rf_bwd_dx");
   LY_CHECK(dug && wg && dx, "rf_bwd_dx: null pointer");
   int gx, gy;
   const RfGeom g = rf_geom(n_img, H, W, C, k, s, (long)n_img * H * W, gx, gy);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (k == 3 && s == 2 && (H & 1) == 0 && (W & 1) == 0 && (C & 7) == 0 && LY_RF_DX_TILED) {
     // LDS-tiled gather (dug read ~1.6x from HBM instead of nine times through L2): 4 x 4 output pixels + halo per block (29 KB bf16 / 58 KB
     // fp32: occupancy decides — 8 x 8 = 93 KB, one block per CU: 248 us; 5 x 5: 120; 4 x 4: 110; 3 x 3: 167; the per-pixel gather: 279)
     const int Ho = H / 2, Wo = W / 2;
+#define RF_DX_T(AV) \
+  LY_EMIT(out, (ly_launch_lds<ly_rf_bwd_dx_s2t_kernel<T, TM, AV>>(grid, dim3(LY_THREADS), lds, out.st, g, RF_CT(dug), wg, RF_T(dx), lddx, addnc, add_scale, tiles_y, tiles_x)), \
+          "ly_rf_bwd_dx_s2t_kernel<%s, %d, " #AV ">", ly_tname<T>(), TM)
     LY_WITH_T(dtype, {
       constexpr int TM = sizeof(T) == 2 ? LY_RF_DX_TM : 4;
       const int tiles_y = (Ho + TM - 1) / TM, tiles_x = (Wo + TM - 1) / TM;
       const size_t lds = (size_t)(TM + 1) * (TM + 1) * 9 * 64 * sizeof(T);
       const dim3 grid((unsigned)(n_img * tiles_y * tiles_x), (unsigned)((C + 63) / 64));
-      if (addnc) return ly_launch_lds<ly_rf_bwd_dx_s2t_kernel<T, TM, 1>>(grid, dim3(LY_THREADS), lds, st, g, RF_CT(dug), wg, RF_T(dx), lddx, addnc, add_scale, tiles_y, tiles_x);
-      return ly_launch_lds<ly_rf_bwd_dx_s2t_kernel<T, TM, 0>>(grid, dim3(LY_THREADS), lds, st, g, RF_CT(dug), wg, RF_T(dx), lddx, addnc, add_scale, tiles_y, tiles_x);
+      return addnc ? RF_DX_T(1) : RF_DX_T(0);
     });
+#undef RF_DX_T
   }
   const int add = !addnc ? 0 : (g.chunk <= (long)H * W ? 2 : 1);
-#define RF_DX(KV, AV) hipLaunchKernelGGL((ly_rf_bwd_dx_kernel<T, KV, AV>), dim3(gx, gy), dim3(LY_THREADS), 0, st, g, RF_CT(dug), wg, RF_T(dx), lddx, addnc, add_scale)
+#define RF_DX(KV, AV)                                                                                                                                        \
+  return LY_EMIT(out, (ly_launch<ly_rf_bwd_dx_kernel<T, KV, AV>>(dim3(gx, gy), dim3(LY_THREADS), 0, out.st, g, RF_CT(dug), wg, RF_T(dx), lddx, addnc, add_scale)), \
+                 "ly_rf_bwd_dx_kernel<%s, " #KV ", " #AV ">", ly_tname<T>())
   LY_WITH_T(dtype, {
     if (k == 3) { if (add == 2) RF_DX(3, 2); else if (add == 1) RF_DX(3, 1); else RF_DX(3, 0); }
     else { if (add == 2) RF_DX(1, 2); else if (add == 1) RF_DX(1, 1); else RF_DX(1, 0); }
   });
 #undef RF_DX
-  LY_LAUNCH_CHECK();
-  return 0;
+}
+
+extern "C" int ly_rf_bwd_dx(int n_img, int H, int W, int C, int k, int s, const void* dug, const float* wg, void* dx, int lddx, const float* addnc,
+                            float add_scale, int dtype, void* stream) {
+  return rf_bwd_dx_entry(n_img, H, W, C, k, s, dug, wg, dx, lddx, addnc, add_scale, dtype, LY_ON_STREAM(stream));
+}
+
+// the arguments of ly_rf_bwd_dx with (name, cap) for the stream
+extern "C" int ly_rf_bwd_dx_describe(int n_img, int H, int W, int C, int k, int s, const void* dug, const float* wg, void* dx, int lddx, const float* addnc,
+                                     float add_scale, int dtype, char* name, int cap) {
+  LY_CHECK(name && cap > 0, "rf_bwd_dx_describe: bad arguments");
+  return rf_bwd_dx_entry(n_img, H, W, C, k, s, dug, wg, dx, lddx, addnc, add_scale, dtype, LyOut{nullptr, name, cap});
 }

@@ -791,21 +791,14 @@ static void wg_plan_group(const LyWgradParams* arr, const int n, WgPlan& S, LyWg
 }
 
 // -------------------------------------------------------------------------------------------------
-// A plan onto the stream, or its kernel's name (LyWgOut): plan fields -> template instantiation
+// A plan onto the stream, or its kernel's name (LyOut): plan fields -> template instantiation
 // -------------------------------------------------------------------------------------------------
-template <auto KERNEL, class... A>
-static int wg_launch_plain(const dim3 grid, hipStream_t st, const A&... args) {
-  hipLaunchKernelGGL(KERNEL, grid, dim3(LY_THREADS), 0, st, args...);
-  LY_LAUNCH_CHECK();
-  return 0;
-}
-
 template <typename T, int BN, int BK, int P>
-static int wg_launch_tiled(const LyWgradParams& Q, const WgPlan& W, const dim3 grid, float* const slab, const LyWgOut& out) {
+static int wg_launch_tiled(const LyWgradParams& Q, const WgPlan& W, const dim3 grid, float* const slab, const LyOut& out) {
   // <ROWS, PRO, OCT>
 #define WG_TILED(ROWS_, PRO_, OCT_)                                                                                                                            \
-  LY_WG_EMIT(out, (ly_launch_lds<ly_wgrad_tiled_kernel<T, BN, BK, P, ROWS_, PRO_, OCT_>>(grid, dim3(LY_THREADS), W.lds, out.st, Q, W.tiles_k, W.chunk_px, slab)), \
-             "ly_wgrad_tiled_kernel<%s, %d, %d, %d, " #ROWS_ ", " #PRO_ ", " #OCT_ ">", LyT<T>::BF ? "__bf16" : "float", BN, BK, P)
+  LY_EMIT(out, (ly_launch_lds<ly_wgrad_tiled_kernel<T, BN, BK, P, ROWS_, PRO_, OCT_>>(grid, dim3(LY_THREADS), W.lds, out.st, Q, W.tiles_k, W.chunk_px, slab)), \
+             "ly_wgrad_tiled_kernel<%s, %d, %d, %d, " #ROWS_ ", " #PRO_ ", " #OCT_ ">", ly_tname<T>(), BN, BK, P)
   if constexpr (LyT<T>::BF) {
     if (W.oct) return !W.rows ? WG_TILED(false, false, true) : W.pro ? WG_TILED(true, true, true) : WG_TILED(true, false, true);
   }
@@ -814,13 +807,13 @@ static int wg_launch_tiled(const LyWgradParams& Q, const WgPlan& W, const dim3 g
 }
 
 template <typename T>
-static int wg_launch(const LyWgradParams& Q, const WgPlan& W, const LyWgOut& out) {
+static int wg_launch(const LyWgradParams& Q, const WgPlan& W, const LyOut& out) {
   constexpr int PX = LyT<T>::BF ? 128 : 64;
-  if (W.kind == WG_W3) return LY_WG_EMIT(out, ly_wgrad3_launch(Q, out.st), "ly_wgrad3_kernel");
+  if (W.kind == WG_W3) return LY_EMIT(out, ly_wgrad3_launch(Q, out.st), "ly_wgrad3_kernel");
   const dim3 grid((unsigned)W.tiles, (unsigned)W.chunks);
   if (W.kind == WG_GENERIC) {
 #define WG_GENERIC_(ROWS_) \
-  LY_WG_EMIT(out, (wg_launch_plain<ly_wgrad_kernel<T, ROWS_>>(grid, out.st, Q, W.tiles_k, W.chunk_px)), "ly_wgrad_kernel<%s, " #ROWS_ ">", LyT<T>::BF ? "__bf16" : "float")
+  LY_EMIT(out, (ly_launch<ly_wgrad_kernel<T, ROWS_>>(grid, dim3(LY_THREADS), 0, out.st, Q, W.tiles_k, W.chunk_px)), "ly_wgrad_kernel<%s, " #ROWS_ ">", ly_tname<T>())
     return W.rows ? WG_GENERIC_(true) : WG_GENERIC_(false);
 #undef WG_GENERIC_
   }
@@ -837,12 +830,12 @@ static int wg_launch(const LyWgradParams& Q, const WgPlan& W, const LyWgOut& out
 }
 
 template <typename T>
-static int wg_launch_group(const WgPlan& S, const LyWgradGroupArgs& G, const LyWgOut& out) {
+static int wg_launch_group(const WgPlan& S, const LyWgradGroupArgs& G, const LyOut& out) {
   constexpr int PX = LyT<T>::BF ? 128 : 64, BN = 128, BK = 128;
   // <PRO, GSLAB, OCT> of the rows form
 #define WG_GROUP(PRO_, GSLAB_, OCT_)                                                                                                                      \
-  LY_WG_EMIT(out, (ly_launch_lds<ly_wgrad_tiled_group_kernel<T, BN, BK, PX, true, PRO_, GSLAB_, OCT_>>(dim3((unsigned)S.chunks), dim3(LY_THREADS), S.lds, out.st, G)), \
-             "ly_wgrad_tiled_group_kernel<%s, %d, %d, %d, true, " #PRO_ ", " #GSLAB_ ", " #OCT_ ">", LyT<T>::BF ? "__bf16" : "float", BN, BK, PX)
+  LY_EMIT(out, (ly_launch_lds<ly_wgrad_tiled_group_kernel<T, BN, BK, PX, true, PRO_, GSLAB_, OCT_>>(dim3((unsigned)S.chunks), dim3(LY_THREADS), S.lds, out.st, G)), \
+             "ly_wgrad_tiled_group_kernel<%s, %d, %d, %d, true, " #PRO_ ", " #GSLAB_ ", " #OCT_ ">", ly_tname<T>(), BN, BK, PX)
   const auto launch = [&]() -> int {
     if (S.kind == WG_W1) return ly_wgrad1_group_launch(G, out);
     if (!S.slab) return S.pro ? WG_GROUP(true, false, false) : WG_GROUP(false, false, false);
@@ -867,20 +860,20 @@ static int wg_launch_group(const WgPlan& S, const LyWgradGroupArgs& G, const LyW
 // Entry points
 // -------------------------------------------------------------------------------------------------
 template <typename T>
-static int wgrad_dispatch(const LyWgradParams& P, const LyWgOut& out) {
+static int wgrad_dispatch(const LyWgradParams& P, const LyOut& out) {
   WgPlan W;
   LY_TRY(wg_plan<T>(P, W));
   return wg_launch<T>(P, W, out);
 }
 
-static int wgrad_one(const LyWgradParams* p, const LyWgOut& out) {
+static int wgrad_one(const LyWgradParams* p, const LyOut& out) {
   LY_CHECK(p, "wgrad: null params");
   LY_CHECK_DTYPE(p->dtype, "wgrad");
   return p->dtype == LY_BF16 ? wgrad_dispatch<__bf16>(*p, out) : wgrad_dispatch<float>(*p, out);
 }
 
 template <typename T>
-static int wgrad_group_dispatch(const LyWgradParams* arr, const int n, const LyWgOut& out) {
+static int wgrad_group_dispatch(const LyWgradParams* arr, const int n, const LyOut& out) {
   WgPlan S;
   LyWgradGroupArgs G;
   wg_plan_group<T>(arr, n, S, G);
@@ -888,7 +881,7 @@ static int wgrad_group_dispatch(const LyWgradParams* arr, const int n, const LyW
 }
 
 // ly_wgrad_group and its description: 0, or — describing a group that is not one launch — 1
-static int wgrad_many(const LyWgradParams* arr, const int n, const LyWgOut& out) {
+static int wgrad_many(const LyWgradParams* arr, const int n, const LyOut& out) {
   LY_CHECK(arr && n > 0, "wgrad_group: bad arguments");
   bool same = n >= 2 && n <= LY_WGRAD_GROUP_MAX;
   for (int g = 0; g < n && same; ++g) {
@@ -905,13 +898,13 @@ static int wgrad_many(const LyWgradParams* arr, const int n, const LyWgOut& out)
   return arr[0].dtype == LY_BF16 ? wgrad_group_dispatch<__bf16>(arr, n, out) : wgrad_group_dispatch<float>(arr, n, out);
 }
 
-extern "C" int ly_wgrad(const LyWgradParams* p, void* stream) { return wgrad_one(p, LyWgOut{reinterpret_cast<hipStream_t>(stream), nullptr, 0}); }
+extern "C" int ly_wgrad(const LyWgradParams* p, void* stream) { return wgrad_one(p, LyOut{reinterpret_cast<hipStream_t>(stream), nullptr, 0}); }
 
 extern "C" int ly_wgrad_group(const LyWgradParams* arr, int n, void* stream) {
-  return wgrad_many(arr, n, LyWgOut{reinterpret_cast<hipStream_t>(stream), nullptr, 0});
+  return wgrad_many(arr, n, LyOut{reinterpret_cast<hipStream_t>(stream), nullptr, 0});
 }
 
 extern "C" int ly_wgrad_describe(const LyWgradParams* arr, int n, char* name, int cap) {
   LY_CHECK(arr && n > 0 && name && cap > 0, "wgrad_describe: bad arguments");
-  return wgrad_many(arr, n, LyWgOut{nullptr, name, cap});
+  return wgrad_many(arr, n, LyOut{nullptr, name, cap});
 }

@@ -3,17 +3,6 @@
 #pragma once
 #include "ly_common.hpp"
 #include "ly_params.h"
-#include <stdio.h>
-
-// Where a planned launch goes: onto the stream — or, with `name` set (ly_wgrad_describe), nowhere: only the contraction kernel's name as
-// rocprofv3 prints it, NUL-terminated in at most `cap` bytes.  LY_WG_EMIT is the one place a template instantiation is chosen from plan
-// fields, so the name stands next to the instantiation it describes.
-struct LyWgOut {
-  hipStream_t st;
-  char* name;
-  int cap;
-};
-#define LY_WG_EMIT(out, launch, ...) ((out).name ? (snprintf((out).name, (size_t)(out).cap, __VA_ARGS__), 0) : (launch))
 
 bool ly_wgrad3_ok(const LyWgradParams& P);                         // ly_wgrad3.hip
 int ly_wgrad3_launch(const LyWgradParams& P, hipStream_t st);
@@ -31,8 +20,8 @@ struct LyWgradGroupArgs {
 
 // ly_wgrad1.hip: the launches of wg_launch / wg_launch_group (ly_wgrad.hip) for a problem the plan found eligible — same grid, chunking and
 // slab; slab == nullptr (one chunk only) adds to dw directly
-int ly_wgrad1_launch(const LyWgradParams& P, int BN, int BK, dim3 grid, int tiles_k, long chunk_px, float* slab, const LyWgOut& out);
-int ly_wgrad1_group_launch(const LyWgradGroupArgs& G, const LyWgOut& out);
+int ly_wgrad1_launch(const LyWgradParams& P, int BN, int BK, dim3 grid, int tiles_k, long chunk_px, float* slab, const LyOut& out);
+int ly_wgrad1_group_launch(const LyWgradGroupArgs& G, const LyOut& out);
 
 // The fold of a slab launch's partial tiles: *d += sum over chunks of p[chunk * E], in a fixed order whatever the block count of the producing
 // launch, one writer per element.  Block = 64 slab columns (threadIdx & 63) x rls row lanes (threadIdx >> 6) that walk the chunks: 16 for

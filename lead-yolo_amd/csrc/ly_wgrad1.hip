@@ -211,16 +211,16 @@ __global__ __launch_bounds__(LY_THREADS) __attribute__((amdgpu_waves_per_eu(W1<1
 }
 
 template <int BN, int BK>
-static int wgrad1_launch_tile(const LyWgradParams& Q, const dim3 grid, const int tiles_k, const long chunk_px, float* const slab, const LyWgOut& out) {
+static int wgrad1_launch_tile(const LyWgradParams& Q, const dim3 grid, const int tiles_k, const long chunk_px, float* const slab, const LyOut& out) {
 #define W1_LAUNCH(SLAB_)                                                                                                                          \
-  LY_WG_EMIT(out, (ly_launch_lds<ly_wgrad1_kernel<BN, BK, SLAB_>>(grid, dim3(LY_THREADS), (size_t)W1<BN, BK>::LDS, out.st, Q, tiles_k, chunk_px, slab)), \
+  LY_EMIT(out, (ly_launch_lds<ly_wgrad1_kernel<BN, BK, SLAB_>>(grid, dim3(LY_THREADS), (size_t)W1<BN, BK>::LDS, out.st, Q, tiles_k, chunk_px, slab)), \
              "ly_wgrad1_kernel<%d, %d, " #SLAB_ ">", BN, BK)
   return slab ? W1_LAUNCH(true) : W1_LAUNCH(false);
 #undef W1_LAUNCH
 }
 
 int ly_wgrad1_launch(const LyWgradParams& Q, const int BN, const int BK, const dim3 grid, const int tiles_k, const long chunk_px, float* const slab,
-                     const LyWgOut& out) {
+                     const LyOut& out) {
   LY_CHECK(chunk_px % W1_PX == 0, "wgrad1: chunk of %ld pixels is not a whole number of steps", chunk_px);
   LY_CHECK(slab || grid.y == 1, "wgrad1: several chunks need the slab");
   if (BN == 128 && BK == 128) return wgrad1_launch_tile<128, 128>(Q, grid, tiles_k, chunk_px, slab, out);
@@ -231,8 +231,8 @@ int ly_wgrad1_launch(const LyWgradParams& Q, const int BN, const int BK, const d
   return 0;
 }
 
-int ly_wgrad1_group_launch(const LyWgradGroupArgs& G, const LyWgOut& out) {
+int ly_wgrad1_group_launch(const LyWgradGroupArgs& G, const LyOut& out) {
   for (int g = 0; g < G.n; ++g) LY_CHECK(G.chunk_px[g] % W1_PX == 0 && G.slab[g], "wgrad1: group member %d has no slab or a ragged chunk", g);
-  return LY_WG_EMIT(out, (ly_launch_lds<ly_wgrad1_group_kernel>(dim3((unsigned)G.blk0[G.n]), dim3(LY_THREADS), (size_t)W1<128, 128>::LDS, out.st, G)),
+  return LY_EMIT(out, (ly_launch_lds<ly_wgrad1_group_kernel>(dim3((unsigned)G.blk0[G.n]), dim3(LY_THREADS), (size_t)W1<128, 128>::LDS, out.st, G)),
                     "ly_wgrad1_group_kernel");
 }

@@ -1137,8 +1137,9 @@ def _rfcbam_backward_streamed(ctx, sv, du, dgo, dbo):
     dx = None
     if ctx.needs_input_grad[1]:
         dx = ops.empty_nhwc(n, c, h, w, xr)
-        with ops._Timed(f"ly_rf_bwd_dx_kernel<{ops._tname(xr)}, {k}>", 0.0, es9 + xr.element_size() * n * h * w * c, valu_flops=2.0 * mo * kk * kk * c):
-            L.check(L.lib().ly_rf_bwd_dx(n, h, w, c, k, s, p(dcd), p(wg), p(dx), c, p(dgap), 1.0 / (h * w), code, st), "ly_rf_bwd_dx")
+        args = (n, h, w, c, k, s, p(dcd), p(wg), p(dx), c, p(dgap), 1.0 / (h * w), code)
+        with ops._Timed(ops._label("ly_rf_bwd_dx_describe", *args), 0.0, es9 + xr.element_size() * n * h * w * c, valu_flops=2.0 * mo * kk * kk * c):
+            L.check(L.lib().ly_rf_bwd_dx(*args, st), "ly_rf_bwd_dx")
     dbias = _rf_dbias(ctx, sv)
     return _rf_grads(ctx, dx, dwa, dwb, _rf_gen_w_fold(ctx, sv, dwg), dgg, dbg, dw18, dwc, dbias, dgo, dbo)
 

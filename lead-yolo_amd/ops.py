@@ -41,9 +41,15 @@ class _Timed:
             PROFILE.append(self.rec)
 
 
-def gemm_config(n_out):
-    """mirror of the tile heuristic in csrc/ly_gemm.hip (ly_gemm_fwd)"""
-    return (4, 2, 4) if n_out > 64 else (4, 1, 4) if n_out > 32 else (2, 2, 1)
+def _label(describe, *args):
+    """the `_Timed` name of a C-ABI call whose kernel the library picks: what the entry's describe twin (include/lead_yolo_hip.h) says it
+    would launch for these arguments, as rocprofv3 prints it.  Asked only while a profile is recorded; a refused call is reported by the
+    launch itself, and where there is no name (a refusal, ly_mlpblock_pconv's "not built" code) the record carries the entry's."""
+    if PROFILE is None:
+        return None
+    name = ctypes.create_string_buffer(160)
+    rc = getattr(capi.lib(), describe)(*args, name, len(name))
+    return name.value.decode() if rc >= 0 and name.value else describe[:-len("_describe")]
 
 
 _CONV_TILE_CACHE = {}
@@ -70,20 +76,6 @@ def pick_conv_tile(h, w, max_px=128, max_frame=192):
 
 
 MLP_WIDTHS = (16, 24, 40, 80, 160, 320)     # C values ly_mlpblock_fwd is instantiated for (include/lead_yolo_hip.h)
-
-
-def mlp_config(c, m, w, bf16=False):
-    """(C, NT, HT, T2D) of the kernel ly_mlpblock_fwd launches -- mirrors dispatch_nt in csrc/ly_mlpblock.hip"""
-    ht = {16: 2, 24: 4, 40: 2, 80: 2, 160: 4, 320: 4}[c]
-    ntmax = {16: 4, 24: 4, 40: 4, 80: 2, 160: 2, 320: 1}[c]
-    if c >= 80:
-        if c == 80 and bf16 and m >= 384 * 256:
-            return c, 4, ht, "false"
-        return c, (2 if ntmax >= 2 and m >= 200 * 128 else 1), ht, "false"
-    if w % 16 == 0 and w >= 64 and ntmax >= 2:
-        return c, 2, ht, "true"
-    nt = 4 if (ntmax >= 4 and m >= 256 * 1024) else 2 if (ntmax >= 2 and m >= 128 * 512) else 1
-    return c, nt, ht, "false"
 
 
 def require_cuda(x, who, mod=None):
@@ -193,38 +185,16 @@ def gemm(*, M, H, W, K, N, a0, lda0, k0, wp, out, ldo, a1=None, lda1=0, gather=G
                           act, _p(out), ldo, _p(stats), code, scat_ks, scat_c, _p(eadd), ldeadd)
     if eadd is not None and eadd.dtype != out.dtype:
         raise ValueError("gemm: eadd must have the output's dtype")
-    nt, mt, wc = gemm_config(N)
-    ti = {GATHER_PATCH_NCHW_U8: "unsigned char", GATHER_PATCH_NCHW_BF16: "ly_bf16img", GATHER_PATCH_NCHW_F16: "ly_f16img"}.get(
-        gather, "float" if (code == 0 or image) else "__bf16")
-    to = "float" if code == 0 else "__bf16"
-    es_i, es_o = {"float": 4, "__bf16": 2, "unsigned char": 1, "ly_bf16img": 2, "ly_f16img": 2}[ti], (4 if to == "float" else 2)
-    kgather = GATHER_PATCH_NCHW if image else gather        # the kernel template's gather code (the uint8 image differs by TI only)
-    # the variant launch_gemm_v (csrc/ly_gemm.hpp) picks: resident weights for K in one / two chunks + the branch-free epilogue
-    nchunk = -(-K // (128 if ti == "__bf16" else 64))
-    nch = 0
-    if N % 4 == 0 and ldo % 4 == 0 and out is not None:
-        ok1 = wc == 4 or pro == 0
-        ok2 = wc == 4 and pro != PRO_GATE
-        if stats is not None:
-            ok1, ok2 = ok1 and pro != PRO_GATE, ok2 and pro == 0
-        nch = 1 if (nchunk == 1 and ok1) else 2 if (nchunk == 2 and ok2) else 0
-    fast = N % 4 == 0 and ldo % 4 == 0 and out is not None
-    ep = (2 if stats is not None else 1) if (nch or (fast and pro == 0)) else 1 if (fast and pro == PRO_GATE and stats is None) else 0
-    if scat_ks or eadd is not None:                         # the scatter / add-before-store epilogues (launch_gemm_v)
-        ep = 4 if eadd is not None else 3
-    name = f"ly_gemm_kernel_d2<{ti}, {to}, {nt}, {mt}, {wc}, {kgather}, {pro}, {nch}, {ep}>"
-    if (image and Cin == 3 and K == 48 and 20 <= N <= 80 and N % 4 == 0 and (out is None or ldo % 4 == 0) and Hin == 4 * H and Win == 4 * W
-            and (code != 0 or gather in (GATHER_PATCH_NCHW, GATHER_PATCH_NCHW_U8))):
-        # ly_patch4_try (csrc/ly_patch4.hip): PatchEmbed on an RGB image has its own LDS-free kernel
-        name = f"ly_patch4_kernel<{ti}, {to}, {max(2, -(-N // 16))}, {'true' if stats is not None else 'false'}>"
-    with _Timed(name, 2.0 * M * K * N, es_i * M * K + (es_o * M * N if out is not None else 0) + 4.0 * N * K):
+    es_i = 1 if gather == GATHER_PATCH_NCHW_U8 else 2 if gather in (GATHER_PATCH_NCHW_BF16, GATHER_PATCH_NCHW_F16) else 4 if (code == 0 or image) else 2
+    es_o = 4 if code == 0 else 2
+    with _Timed(_label("ly_gemm_describe", ctypes.byref(P)), 2.0 * M * K * N, es_i * M * K + (es_o * M * N if out is not None else 0) + 4.0 * N * K):
         capi.check(capi.lib().ly_gemm_fwd(ctypes.byref(P), capi.stream_ptr()), "ly_gemm_fwd")
 
 
 def mlpblock_pconv(x, z, n, h, w, c, wp):
     """z = [conv3x3(x[:, :c/4]; wp) | x[:, c/4:]] in one pass (persistent MLPBlock kernel, partial conv only); x, z dense NHWC [n, c, h, w].
     Returns False when the kernel is not built for this shape (the caller then copies and calls conv3x3)."""
-    with _Timed(f"ly_mlpblock_persist_kernel<{_tname(x)}, {c}, pconv>", 18.0 * n * h * w * (c // 4) ** 2, 2.0 * x.element_size() * n * h * w * c):
+    with _Timed(_label("ly_mlpblock_pconv_describe", n, h, w, c, capi.dtype_code(x)), 18.0 * n * h * w * (c // 4) ** 2, 2.0 * x.element_size() * n * h * w * c):
         rc = capi.lib().ly_mlpblock_pconv(_p(x), _p(z), n, h, w, c, _p(wp), capi.dtype_code(x), capi.stream_ptr())
     if rc < 0:
         capi.check(rc, "ly_mlpblock_pconv")
@@ -235,13 +205,7 @@ def conv3x3(*, M, H, W, Cin, N, x, ldx, wp, out, ldo, e_scale=None, e_shift=None
     th, tw = pick_conv_tile(H, W)
     code = capi.dtype_code(x)
     P = capi.LyConv3Params(M, H, W, Cin, N, th, tw, _p(x), ldx, _p(wp), _p(e_scale), _p(e_shift), act, _p(out), ldo, _p(stats), code)
-    mt, wc = (2, 4) if N > 64 else (2, 2)
-    ntv = -(-(th * tw) // 16)                               # active pixel tiles of a patch: compile-time in the bf16 instantiations (conv3_dispatch)
-    nta = 0 if code == 0 else (ntv if (wc == 4 and ntv in (5, 8)) else 4 if (wc == 2 and ntv == 8) else 0)
-    name = f"ly_conv3x3_kernel<{_tname(x)}, {mt}, {wc}, {nta}>"
-    if code != 0 and N > 64 and (M // (H * W)) * -(-W // tw) * -(-H // th) * -(-N // 128) < 512:
-        name = "ly_conv3x3_lat_kernel<__bf16, 2, 2>"        # conv3_dispatch (csrc/ly_conv3x3.hip): grids under two blocks per CU take the latency form
-    with _Timed(name, 2.0 * M * 9 * Cin * N, x.element_size() * M * (Cin + N) + 4.0 * 9 * Cin * N):
+    with _Timed(_label("ly_conv3x3_describe", ctypes.byref(P)), 2.0 * M * 9 * Cin * N, x.element_size() * M * (Cin + N) + 4.0 * 9 * Cin * N):
         capi.check(capi.lib().ly_conv3x3_fwd(ctypes.byref(P), capi.stream_ptr()), "ly_conv3x3_fwd")
 
 
@@ -332,6 +296,10 @@ def _tname(t):
     return "float" if t.dtype == torch.float32 else "__bf16"
 
 
+def _bname(flag):
+    return "true" if flag else "false"
+
+
 def pool_hw(x, ldx, n, h, w, c):
     pool = torch.empty((n, h + w, c), dtype=torch.float32, device=x.device)
     with _Timed(f"ly_pool_hw_kernel<{_tname(x)}>", 1.0 * n * h * w * c, x.element_size() * n * h * w * c):
@@ -355,7 +323,8 @@ def coordatt_mlp_bwd(pool, n, h, w, c, mip, w1, b1, mean, invstd, gamma, beta, w
     sums = zeros_f64(32 * 2 * mip, pool.device)                        # striped (sum dy1, sum dy1*xh), double accumulators
     ws = torch.empty(r * 3 * mip, dtype=torch.float32, device=pool.device)
     dpool = torch.empty((n, h + w, c), dtype=torch.float32, device=pool.device)
-    with _Timed("ly_coordatt_mlp_bwd1_kernel + bwd2", 8.0 * r * c * mip, 4.0 * 4 * r * c):
+    # (two launches: the record carries the second, whose instantiation `mip` alone fixes; ly_coordatt_mlp_bwd1_kernel<mip, NS> runs ahead of it)
+    with _Timed(f"ly_coordatt_mlp_bwd2_kernel<{mip}>", 8.0 * r * c * mip, 4.0 * 4 * r * c):
         capi.check(capi.lib().ly_coordatt_mlp_bwd(_p(pool), n, h, w, c, mip, _p(w1), _p(b1), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(wh), _p(ww),
                                                   _p(a_h), _p(a_w), _p(da_h), _p(da_w), _p(ws), _p(sums), _p(dpool),
                                                   *[_p(t) for t in targets], int(targets[0].dtype == torch.float64), capi.stream_ptr()),
@@ -480,8 +449,8 @@ def rf3m_fwd(*, n, h, w, c, ho, wo, N, s, th, tw, x, ldx, ca, rfa, wp, e_scale, 
     P = capi.LyRfcbam3Params(n, h, w, c, ho, wo, N, s, th, tw, _p(x), ldx, None, _p(ca), _p(rfa), _p(wp), _p(e_scale),
                              _p(e_shift), _p(out), ldo, None, 0, capi.dtype_code(x))
     mo = n * ho * wo
-    mt = 4 if N % 128 == 0 else 2
-    with _Timed(f"ly_rf3m_fwd_kernel<{mt}>", 2.0 * mo * 9 * c * N + 2.0 * mo * (N // (32 * mt)) * (c // 4) * 6 * 32 * 16,
+    mt = 4 if N % 128 == 0 else 2                          # (32-channel tiles per block of pack.rf3m_stream's weight stream: the flop count's)
+    with _Timed(_label("ly_rf3m_fwd_describe", ctypes.byref(P)), 2.0 * mo * 9 * c * N + 2.0 * mo * (N // (32 * mt)) * (c // 4) * 6 * 32 * 16,
                 x.element_size() * (n * h * w * c + mo * N) + 2.0 * 9 * c * N):
         capi.check(capi.lib().ly_rf3m_fwd(ctypes.byref(P), capi.stream_ptr()), "ly_rf3m_fwd")
 
@@ -512,8 +481,7 @@ def pick_tile_bwd_dx(ho, wo, o):
         ih, iw = 2 * (th - 1) + 3, 2 * (tw - 1) + 3
         pos = ih * iw
         nct = -(-wo // tw)
-        lds = 2 * pos * 128 + 288 * 128 + 64 * (2 * o + 16) + 32 * 9 * 8 * 4 + 256 + (ih + 2 * tw * nct + 2 + 27) * 128     # mirrors rb_launch
-        if th < 1 or pos > 320 or lds > 160 * 1024:
+        if th < 1 or pos > 320 or capi.lib().ly_rf3c_bwd_lds(2, th, tw, wo, o) > 160 * 1024:
             continue
         its = sum(-(-(((th + 1 - ry) // 2) * ((tw // 2 + 1 - rx) // 2)) // 8) for ry in (0, 1) for rx in (0, 1))
         key = (-(-ho // th) * nct * its, pos)
@@ -538,9 +506,7 @@ def rf3c_fwd(*, n, h, w, c, ho, wo, N, s, th, tw, x, ldx, wq, ca, rfa, wp, e_sca
     P = capi.LyRfcbam3Params(n, h, w, c, ho, wo, N, s, th, tw, _p(x), ldx, None, _p(ca), _p(rfa), _p(wp), _p(e_scale),
                              _p(e_shift), _p(out), ldo, _p(stats), int(linear), capi.dtype_code(x))
     mo = n * ho * wo
-    bf = x.dtype == torch.bfloat16
-    cfg = "2, 8" if (N > 128 and bf) else ("2, 4" if N > 64 else "1, 4")         # mirrors rc_dispatch_fwd
-    with _Timed(f"ly_rf3c_fwd_kernel<{_tname(x)}, {cfg}, {s}, {'true' if raw else 'false'}>", 2.0 * mo * 9 * c * N,
+    with _Timed(_label("ly_rf3c_fwd_describe", ctypes.byref(P), _p(wq), int(raw)), 2.0 * mo * 9 * c * N,
                 x.element_size() * (n * h * w * c + mo * N) + 4.0 * 9 * c * N, valu_flops=2.0 * mo * 81 * c):
         capi.check(capi.lib().ly_rf3c_fwd(ctypes.byref(P), _p(wq), int(raw), capi.stream_ptr()), "ly_rf3c_fwd")
 
@@ -560,10 +526,10 @@ def rfcbam_stats(x, ldx, n, h, w, c, k, s, wg=None, a1=None, b1=None, th=1, tw=6
                                       "than the separate ly_colsum launch it saved: measured 44 -> 69 us)")
         slices = max(1, min(h * w // PRE1_PIXELS, 128))    # a function of the map only: results do not change with the batch split
         part = torch.empty((n, slices, c), dtype=torch.float32, device=x.device)
-    with _Timed((f"ly_rfcbam_pre1_kernel<{_tname(x)}>" if (gap and k == 1) else f"ly_rfcbam_stats{k}_kernel<{_tname(x)}>"), 0.0,
+    args = (_p(x), ldx, n, h, w, c, k, s, _p(wg), _p(a1), _p(b1), th, tw, _p(mm), _p(part), slices, capi.dtype_code(x))
+    with _Timed(_label("ly_rfcbam_stats_describe", *args), 0.0,
                 x.element_size() * n * h * w * c + 4.0 * 2 * k * k * n * ho * wo, valu_flops=2.0 * n * ho * wo * c * (81 if k == 3 else 1)):
-        capi.check(capi.lib().ly_rfcbam_stats(_p(x), ldx, n, h, w, c, k, s, _p(wg), _p(a1), _p(b1), th, tw, _p(mm), _p(part), slices,
-                                              capi.dtype_code(x), capi.stream_ptr()), "ly_rfcbam_stats")
+        capi.check(capi.lib().ly_rfcbam_stats(*args, capi.stream_ptr()), "ly_rfcbam_stats")
     return (mm, part) if gap else mm
 
 
@@ -590,10 +556,8 @@ def rfa_map(mm, w18):
 def rfcbam3(*, n, h, w, c, ho, wo, N, s, th, tw, x, ldx, wg, ca, rfa, wp, e_scale, e_shift, out, ldo, stats=None, linear=False):
     P = capi.LyRfcbam3Params(n, h, w, c, ho, wo, N, s, th, tw, _p(x), ldx, _p(wg), _p(ca), _p(rfa), _p(wp), _p(e_scale),
                              _p(e_shift), _p(out), ldo, _p(stats), int(linear), capi.dtype_code(x))
-    mt = 4 if N > 128 else (2 if N > 64 else 1)            # mirrors ly_rfcbam3_fwd
     mo = n * ho * wo
-    sw = mt == 4 and n * -(-ho // th) * -(-wo // tw) * -(-N // 256) > 256    # mirrors launch_rf3: weights via the scalar cache
-    with _Timed(f"ly_rfcbam3{'_sw' if sw else ''}_kernel<{_tname(x)}, {mt}>", 2.0 * mo * 9 * c * N,
+    with _Timed(_label("ly_rfcbam3_describe", ctypes.byref(P)), 2.0 * mo * 9 * c * N,
                 x.element_size() * (n * h * w * c + mo * N) + 4.0 * 9 * c * N, valu_flops=2.0 * mo * 81 * c):
         capi.check(capi.lib().ly_rfcbam3_fwd(ctypes.byref(P), capi.stream_ptr()), "ly_rfcbam3_fwd")
 
@@ -632,7 +596,7 @@ def detect_level(x, ldx, n, h, w, k, wp, bias, na, no, anchors, stride, p, z, zr
     """head 1x1 convolution + decode of one Detect level in ONE launch (ly_detect_level): x rows [n*h*w, k] -> p [n, na, h, w, no], z rows
     (z None: raw maps only).  nat: wp from pack.frag_pack_nat, else the frag_pack3 layout (>= 32 rows)"""
     es = x.element_size()
-    with _Timed(f"ly_detect_level_kernel<{_tname(x)}, {k // 32}>", 2.0 * n * h * w * k * 32, es * n * h * w * k + 8.0 * n * h * w * na * no):
+    with _Timed(f"ly_detect_level_kernel<{_tname(x)}, {k // 32}, {_bname(nat)}, false>", 2.0 * n * h * w * k * 32, es * n * h * w * k + 8.0 * n * h * w * na * no):
         capi.check(capi.lib().ly_detect_level(_p(x), ldx, n, h, w, k, _p(wp), int(nat), _p(bias), na, no, _p(anchors), float(stride), _p(p), _p(z), zrows, zoff,
                                               capi.dtype_code(x), capi.stream_ptr()), "ly_detect_level")
 
@@ -647,7 +611,7 @@ def detect_level_aug(x, ldx, n, h, w, k, wp, bias, na, no, anchors, stride, z, z
     """ly_detect_level with the _descale_pred step of test-time augmentation on the decoded rows: z[..., :4] / dscale, then x = img_w - x when
     dflip; no raw maps"""
     es = x.element_size()
-    with _Timed(f"ly_detect_level_kernel<{_tname(x)}, {k // 32}>", 2.0 * n * h * w * k * 32, es * n * h * w * k + 4.0 * n * h * w * na * no):
+    with _Timed(f"ly_detect_level_kernel<{_tname(x)}, {k // 32}, {_bname(nat)}, true>", 2.0 * n * h * w * k * 32, es * n * h * w * k + 4.0 * n * h * w * na * no):
         capi.check(capi.lib().ly_detect_level_aug(_p(x), ldx, n, h, w, k, _p(wp), int(nat), _p(bias), na, no, _p(anchors), float(stride), None, _p(z),
                                                   zrows, zoff, float(dscale), int(dflip), float(img_w), capi.dtype_code(x), capi.stream_ptr()),
                    "ly_detect_level_aug")
@@ -856,14 +820,7 @@ class SmallGrad:
 
 def mlpblock(x, y, n, h, w, c, wp, w1, w2, sc, sh, stats=None):
     m = n * h * w
-    cc, nt, ht, t2d = mlp_config(c, m, w, x.dtype == torch.bfloat16)
-    kind = "_ring" if c >= 80 else "_occ4" if (c <= 24 and t2d == "true") else ""
-    name = f"ly_mlpblock_fwd{kind}_kernel<{_tname(x)}, {cc}, {nt}, {ht}, {t2d}, {'true' if stats is not None else 'false'}>"
-    if c == 80 and x.dtype == torch.bfloat16 and m >= 128 * 256 and (256 + 2 * w + 2) * 5 <= 2048:
-        name = f"ly_mlpblock_res_kernel<__bf16, 80, 2, 2, {'true' if stats is not None else 'false'}, 4>"      # ly_mlp_dispatch_80 (csrc/ly_mlpblock_b.hip)
-    elif c < 80 and w % 16 == 0 and w >= 32 and n * -(-h // 8) * (w // 16) >= 1024 and (x.dtype == torch.bfloat16 or c < 40):
-        name = f"ly_mlpblock_persist_kernel<{_tname(x)}, {c}, 2, {ht}, {1 if stats is not None else 0}, 1>"      # dispatch_nt_t: the persistent patch walk
-    with _Timed(name, 2.0 * m * (9 * (c // 4) ** 2 + 4 * c * c),
+    with _Timed(_label("ly_mlpblock_fwd_describe", n, h, w, c, capi.dtype_code(x), int(stats is not None)), 2.0 * m * (9 * (c // 4) ** 2 + 4 * c * c),
                 x.element_size() * (1 if stats is not None else 2) * m * c + 4.0 * (9 * (c // 4) ** 2 + 4 * c * c)):
         capi.check(capi.lib().ly_mlpblock_fwd(_p(x), _p(y), n, h, w, c, _p(wp), _p(w1), _p(w2), _p(sc), _p(sh), _p(stats), capi.dtype_code(x),
                                               capi.stream_ptr()), "ly_mlpblock_fwd")
@@ -892,7 +849,7 @@ def mlpblock_bwd(x, dy, n, h, w, c, wp, w1, w2t, w1t, a, b, *, stats=None, g=Non
     slab = None if p1 else _mlpblock_bwd_slab(c, x.device)
     hid = 2 * c
     flops = 2.0 * m * (9 * (c // 4) ** 2 + (2 if p1 else 5) * c * hid)
-    with _Timed(f"ly_mlpblock_bwd_kernel<{c}, pass {1 if p1 else 2}>", flops, x.element_size() * (2 if p1 else 3) * m * c + 4.0 * (9 * (c // 4) ** 2 + 2 * c * hid)):
+    with _Timed(_label("ly_mlpblock_bwd_describe", n, h, w, c, capi.dtype_code(x), 1 if p1 else 2), flops, x.element_size() * (2 if p1 else 3) * m * c + 4.0 * (9 * (c // 4) ** 2 + 2 * c * hid)):
         capi.check(capi.lib().ly_mlpblock_bwd(_p(x), _p(dy), _p(g), n, h, w, c, _p(wp), _p(w1), _p(w2t), _p(w1t), _p(a), _p(b), _p(alpha), _p(kappa), _p(lam),
                                               _p(stats), _p(slab), slab.numel() if slab is not None else 0, _p(dw1), _p(dw2), 1 if p1 else 2,
                                               capi.dtype_code(x), capi.stream_ptr()), "ly_mlpblock_bwd")
@@ -909,7 +866,7 @@ def mlpblock_bwd_dx(g, dy, x, n, h, w, c, wpt, dwp=None, lddw=0, dw_ts=0, dw_cs=
     dx = torch.empty_like(dy)
     m = n * h * w
     slab = _mlpblock_bwd_slab(c, x.device) if (dwp is not None and capi.lib().ly_mlpblock_bwd_slab_floats(c) > 0) else None
-    with _Timed(f"ly_mlpblock_bwd_dx_kernel<{c}>", 2.0 * m * 18 * (c // 4) ** 2, x.element_size() * m * (3 * c + c // 4) + 4.0 * 9 * (c // 4) ** 2):
+    with _Timed(_label("ly_mlpblock_bwd_dx_describe", n, h, w, c, capi.dtype_code(x), int(slab is not None)), 2.0 * m * 18 * (c // 4) ** 2, x.element_size() * m * (3 * c + c // 4) + 4.0 * 9 * (c // 4) ** 2):
         rc = capi.lib().ly_mlpblock_bwd_dx(_p(g), _p(dy), _p(x), _p(dx), n, h, w, c, _p(wpt), _p(slab), slab.numel() if slab is not None else 0,
                                            _p(dwp if slab is not None else None), lddw, dw_ts, dw_cs, capi.dtype_code(x), capi.stream_ptr())
     if rc < 0:
@@ -1166,8 +1123,9 @@ def rfcbam_gen_prepare(x, ldx, n, h, w, c, k, s, gen_w, bn):
     dev = x.device
     if k == 3:
         mom = zeros_f64(54 * c, dev)
-        with _Timed(f"ly_rfcbam_tap_moments_kernel<{_tname(x)}>", 108.0 * n * h * w * c / (s * s), x.element_size() * n * h * w * c):
-            capi.check(capi.lib().ly_rfcbam_tap_moments(_p(x), ldx, n, h, w, c, s, _p(mom), capi.dtype_code(x), capi.stream_ptr()), "ly_rfcbam_tap_moments")
+        args = (_p(x), ldx, n, h, w, c, s, _p(mom), capi.dtype_code(x))
+        with _Timed(_label("ly_rfcbam_tap_moments_describe", *args), 108.0 * n * h * w * c / (s * s), x.element_size() * n * h * w * c):
+            capi.check(capi.lib().ly_rfcbam_tap_moments(*args, capi.stream_ptr()), "ly_rfcbam_tap_moments")
         ho, wo = (h + 2 - 3) // s + 1, (w + 2 - 3) // s + 1
         count = n * ho * wo
     else:
@@ -1239,18 +1197,8 @@ def wgrad(*, M, H, W, N, du, lddu, x, ldx, Hin, Win, Cin, dw, lddw, ks=1, stride
     if not _now and _wgrad_deferrable(q):
         return _wgrad_enqueue(q)
     P = _wgrad_params(**q)
-    with _Timed(_wgrad_label(ctypes.byref(P), 1), 2.0 * M * N * ks * ks * Cin, x.element_size() * M * (N + Cin) + 4.0 * N * ks * ks * Cin):
+    with _Timed(_label("ly_wgrad_describe", ctypes.byref(P), 1), 2.0 * M * N * ks * ks * Cin, x.element_size() * M * (N + Cin) + 4.0 * N * ks * ks * Cin):
         capi.check(capi.lib().ly_wgrad(ctypes.byref(P), capi.stream_ptr()), "ly_wgrad")
-
-
-def _wgrad_label(arr, n):
-    """the `_Timed` name of ly_wgrad (n = 1) / ly_wgrad_group on these LyWgradParams: the kernel the library says it would launch, as
-    rocprofv3 prints it (ly_wgrad_describe).  Asked only while a profile is recorded; a refused problem is reported by the launch itself."""
-    if PROFILE is None:
-        return None
-    name = ctypes.create_string_buffer(128)
-    rc = capi.lib().ly_wgrad_describe(arr, n, name, len(name))
-    return name.value.decode() if rc >= 0 else "ly_wgrad"
 
 
 def _wgrad_params(*, M, H, W, N, du, lddu, x, ldx, Hin, Win, Cin, dw, lddw, ks=1, stride=1, pad=0, nchw=False, up2=False, du_off=0, x_off=0,
@@ -1383,7 +1331,7 @@ def wgrad_group(problems, _now=False):
         return
     arr = (capi.LyWgradParams * len(problems))(*[_wgrad_params(**q) for q in problems])
     x0 = problems[0]["x"]
-    with _Timed(_wgrad_label(arr, len(problems)), sum(2.0 * q["M"] * q["N"] * q["Cin"] for q in problems),
+    with _Timed(_label("ly_wgrad_describe", arr, len(problems)), sum(2.0 * q["M"] * q["N"] * q["Cin"] for q in problems),
                 sum(x0.element_size() * q["M"] * (q["N"] + q["Cin"]) + 4.0 * q["N"] * q["Cin"] for q in problems)):
         capi.check(capi.lib().ly_wgrad_group(arr, len(problems), capi.stream_ptr()), "ly_wgrad_group")
 
@@ -1448,9 +1396,9 @@ def patch4_wgrad_u8(img, du, lddu, n_out, dw, scale):
     n, c, h, w = img.shape
     m = n * (h // 4) * (w // 4)
     ws = wgrad_workspace(img.device)
-    with _Timed("ly_patch4_wgrad_u8_kernel", 2.0 * m * n_out * 48, 1.0 * n * c * h * w + 2.0 * m * n_out + 4.0 * n_out * 48):
-        capi.check(capi.lib().ly_patch4_wgrad_u8(_p(img), n, c, h, w, _p(du), lddu, n_out, float(scale), _p(ws), ws.numel(), _p(dw), capi.dtype_code(du),
-                                                 capi.stream_ptr()), "ly_patch4_wgrad_u8")
+    args = (_p(img), n, c, h, w, _p(du), lddu, n_out, float(scale), _p(ws), ws.numel(), _p(dw), capi.dtype_code(du))
+    with _Timed(_label("ly_patch4_wgrad_u8_describe", *args), 2.0 * m * n_out * 48, 1.0 * n * c * h * w + 2.0 * m * n_out + 4.0 * n_out * 48):
+        capi.check(capi.lib().ly_patch4_wgrad_u8(*args, capi.stream_ptr()), "ly_patch4_wgrad_u8")
 
 
 def coordatt_gate_bwd(dout, x, ldx, n, h, w, c, a_h, a_w, ldd=None):
