@@ -808,7 +808,7 @@ int ly_f64_add(const LyF64AddTable* t, void* stream);
 int ly_rf3s_bwd(const LyRf1BwdParams* p, int Ho, int Wo, int pass, void* stream);
 
 /* ---- detection loss on device (utils/loss.py:121-268 ComputeLoss / build_targets, utils/metrics.py:293-354 EIoU) --------
- * One pyramid level, forward and gradient (no focal loss): anchor matching with the reference's candidate order
+ * One pyramid level, forward and gradient (focal loss, gr, sort_obj_iou and autobalance: the _opts entry points below): anchor matching with the reference's candidate order
  * (offset k, anchor a, target t), EIoU box loss with analytic gradient, per-cell "last writer wins" objectness target (the
  * highest candidate index, i.e. the reference's sequential CPU semantics), BCE objectness (positive weight obj_pw) and — when
  * nc = no - 5 > 1 — the class BCE of every matched row (utils/loss.py:168-173: targets cn, cp at the row's class; positive weight cls_pw;
@@ -832,6 +832,29 @@ int ly_loss_level(const float* p, float* dp, const float* anchors, const float* 
  * from acc [nl][16]; cells / balance: [nl] floats                                                                           */
 int ly_loss_finish(const float* acc, int nl, const float* cells, const float* balance, float box_gain, float obj_gain, float cls_gain, int nc,
                    int bs, float* out, void* stream);
+/* The same two calls with the remaining options of the reference's recipe (utils/loss.py:36-61 FocalLoss, :104-119, :158-181); the two entry
+ * points above forward here with the neutral values fl_gamma = 0, gr = 1, sort_obj_iou = 0, balance_dev = NULL, for which every kernel runs
+ * the instruction sequence it ran before these options existed.  Still three launches per level and one finish, no host sync.
+ *   fl_gamma  > 0: FocalLoss(BCEWithLogitsLoss(pos_weight), gamma = fl_gamma, alpha = fl_alpha) replaces both BCEs (objectness; classes when
+ *             nc > 1), value and gradient, the modulating factor's own derivative included; targets are soft (tobj, cp / cn).  With
+ *             u = 1 - p_t: where u == 0 (exp(-|x|) underflows) the term gamma u^(gamma - 1) du/dx is taken as 0 — torch gives inf * 0 for gamma < 1.
+ *             0: plain BCE, fl_alpha unused (the reference wraps the BCEs only `if g > 0`).
+ *   fl_alpha  in [0, 1]: weight of the positive side, z alpha + (1 - z)(1 - alpha); the reference's recipe uses 0.25
+ *   gr        in [0, 1]: objectness target (1 - gr) + gr * max(iou, 0); 1 = the iou itself
+ *   sort_obj_iou != 0: a cell takes the MAXIMUM of its candidates' values (what the reference's ascending argsort before the assignment
+ *             leaves) instead of the last writer's: integer atomic maximum on the float's bits in the zeroed tobj; winner is not read
+ *   balance_dev  NULL, or double[nl] on the device (8-byte aligned): the autobalanced level weights.  ly_loss_level_opts reads
+ *             balance_dev[level] for the objectness gradient (the scalar `balance` is then unused; `level` = index of this pyramid level);
+ *             ly_loss_finish_opts forms lobj with the same, not yet updated values (`balance` may then be NULL), and then updates in place:
+ *             balance_dev[i] = balance_dev[i] * 0.9999 + 0.0001 / obji (obji = the level's mean objectness loss; 0 gives Inf, as the
+ *             reference's division does), and finally divides the vector by balance_dev[ssi]
+ *   ssi       index of the stride-16 level (used only with balance_dev)                                                              */
+int ly_loss_level_opts(const float* p, float* dp, const float* anchors, const float* targets, int bs, int na, int ny, int nx, int no, long nt,
+                       float anchor_t, float box_gain, float obj_gain, float balance, float* tobj, int* winner, long* cand_cell, float* cand,
+                       float* acc, float* tbox, int match_only, float cls_gain, float cp, float cn, float cls_pw, float obj_pw, float fl_gamma,
+                       float fl_alpha, float gr, int sort_obj_iou, const double* balance_dev, int level, void* stream);
+int ly_loss_finish_opts(const float* acc, int nl, const float* cells, const float* balance, float box_gain, float obj_gain, float cls_gain, int nc,
+                        int bs, float* out, double* balance_dev, int ssi, void* stream);
 
 /* ---- fused multi-tensor optimiser step (train.py:330-341; utils/torch_utils.py:318-346 smart_optimizer, 404-432 ModelEMA) ----------
  * One table entry per state tensor (all pointers DEVICE, fp32).  Entries with a gradient take clip + SGD-nesterov + zero_grad

@@ -1,6 +1,8 @@
 // Detection loss of one pyramid level, forward AND gradient in three launches (reference utils/loss.py:121-268
 // `ComputeLoss.__call__` / `build_targets`, utils/metrics.py:293-354 `bbox_iou(EIoU=True)`); any nc (class BCE with label smoothing and
-// cls_pw when nc > 1, utils/loss.py:168-173), obj_pw, no focal loss.
+// cls_pw when nc > 1, utils/loss.py:168-173), obj_pw; and the options of the reference's recipe: focal loss on both BCEs (fl_gamma > 0,
+// utils/loss.py:36-61 FocalLoss, alpha 0.25), gr < 1, sort_obj_iou and autobalance — uniform branches on kernel arguments, the default
+// path (gamma 0, gr 1, no sort, no device balance) keeps its instruction sequence and its bits.
 //
 // The reference runs ~150 tiny ops forward and ~250 backward per step here (anchor matching with boolean indexing — a
 // host sync per level —, EIoU, two BCEs): 3.4 ms + 4.2 ms of pure launch latency at bs=64, a fifth of the training step.
@@ -16,6 +18,21 @@
 //   ly_loss_obj     per cell: BCE-with-logits against tobj, its gradient into dpred[..., 4], level sum by block reduction.
 // ly_loss_finish combines the level accumulators into (loss, lbox, lobj, lcls) exactly as the reference does (mean per level,
 // balance [4, 1, 0.4], * hyp gains, * batch size).
+//
+// Focal loss: FocalLoss(BCEWithLogitsLoss(pos_weight), gamma, alpha) per element, with s = sigmoid(x) and a SOFT target z (tobj in [0, 1],
+// cp / cn):  u = 1 - p_t = z (1 - s) + (1 - z) s,  af = z alpha + (1 - z)(1 - alpha),  loss = bce * af * u^gamma,
+//   d loss / dx = af * [ bce' * u^gamma - bce * gamma * u^(gamma - 1) * (2z - 1) * s (1 - s) ]      (the modulating factor's own derivative included,
+// as the reference's autograd includes it).  1 - s is taken as sigmoid(-x), not as a float subtraction, so u keeps its relative precision for
+// large |x| and reaches 0 only where exp(-|x|) underflows.  Where u == 0 the second term is taken as 0 — a deliberate difference: torch
+// evaluates 0^(gamma - 1) * 0 = inf * 0 = NaN there for gamma < 1.
+// gr < 1: the elected candidate writes tobj = (1 - gr) + gr * max(iou, 0).
+// sort_obj_iou: the reference sorts the level's candidates by ascending iou before `tobj[b,a,gj,gi] = iou`, i.e. a cell keeps the MAXIMUM
+// of its candidates' values (equal values tie invisibly): an integer atomicMax on the bit pattern of the non-negative float into the zeroed
+// tobj — monotone because the values are >= 0 — replaces the last-writer election; no sort, no winner index.
+// autobalance: the balance vector lives on the device as double[nl] (the reference's is a list of Python floats; its per-level .item() would
+// be a host sync).  ly_loss_obj reads its level's entry for the gradient scale — the value BEFORE this call's update, as in the reference —
+// and ly_loss_finish, after forming lobj with the old values, does balance[i] = balance[i] * 0.9999 + 0.0001 / obji and divides the vector
+// by balance[ssi] (ssi = the stride-16 level).  obji == 0 divides by zero as in the reference: the Inf propagates.
 //
 // The three loss sums of a level are ORDER-INDEPENDENT: every term (a candidate's 1 - eiou and class BCE, a block's objectness partial — itself
 // a fixed-order sum) is converted to 2^-30 fixed point on its own and added with a 64-bit INTEGER atomic, so two runs on the same inputs give the
@@ -92,6 +109,9 @@ struct LyLossLevel {
   float* acc;            // [LY_LOSS_ACC], zeroed, 8-byte aligned: see LY_LOSS_ACC
   float* tbox;           // optional [5*na*nt][4]: (gx - gi, gy - gj, gw, gh) of every valid candidate (build_targets' tbox)
   float cp, cn, cls_pw, obj_pw;      // class targets (label smoothing: 1 - eps/2, eps/2), positive weights of the two BCEs
+  float gamma, alpha;    // focal loss on both BCEs when gamma > 0 (alpha: weight of the positive side)
+  float gr;              // tobj = (1 - gr) + gr * max(iou, 0) when gr < 1
+  int sort;              // sort_obj_iou: a cell keeps the maximum of its candidates instead of the last writer's value
 };
 
 // BCE-with-logits with a positive weight (torch.nn.BCEWithLogitsLoss(pos_weight = pw)): value and d/dx
@@ -102,6 +122,22 @@ __device__ __forceinline__ float ly_bce(float x, float z, float pw) {
 __device__ __forceinline__ float ly_bce_grad(float x, float z, float pw) {
   const float sg = ly_sigmoid(x);
   return (1.f - z) * sg - pw * z * (1.f - sg);
+}
+
+// FocalLoss(BCEWithLogitsLoss(pos_weight = pw), gamma, alpha) of one element: value, and d/dx into *grad (see the head of the file)
+__device__ __forceinline__ float ly_focal(float x, float z, float pw, float gamma, float alpha, float* grad) {
+  const float e = __expf(-fabsf(x)), r = 1.f / (1.f + e);
+  const float big = r, small = e * r;                                    // sigmoid(|x|), sigmoid(-|x|): neither is a difference from 1
+  const float s = x >= 0.f ? big : small, sn = x >= 0.f ? small : big;   // s = sigmoid(x), sn = 1 - s
+  const float sp = log1pf(e) + fmaxf(-x, 0.f);
+  const float bce = (1.f - z) * x + (1.f + (pw - 1.f) * z) * sp;
+  const float dbce = (1.f - z) * s - pw * z * sn;
+  const float u = z * sn + (1.f - z) * s;
+  const float af = z * alpha + (1.f - z) * (1.f - alpha);
+  const float m = powf(u, gamma);
+  const float dm = u > 0.f ? gamma * (m / u) * (1.f - 2.f * z) * (s * sn) : 0.f;     // u == 0: the term is taken as 0 (torch: inf * 0)
+  *grad = af * (dbce * m + bce * dm);
+  return bce * af * m;
 }
 
 __global__ __launch_bounds__(LY_THREADS) void ly_loss_match_kernel(const LyLossLevel L) {
@@ -163,7 +199,12 @@ __global__ __launch_bounds__(LY_THREADS) void ly_loss_match_kernel(const LyLossL
     if (nc > 1) {                                                          // class BCE of this matched row (utils/loss.py:168-173)
       const int cls = (int)tg[1];
       float sc = 0.f;
-      for (int q = 0; q < nc; ++q) sc += ly_bce(pr[5 + q], q == cls ? L.cp : L.cn, L.cls_pw);
+      if (L.gamma > 0.f) {
+        float unused;
+        for (int q = 0; q < nc; ++q) sc += ly_focal(pr[5 + q], q == cls ? L.cp : L.cn, L.cls_pw, L.gamma, L.alpha, &unused);
+      } else {
+        for (int q = 0; q < nc; ++q) sc += ly_bce(pr[5 + q], q == cls ? L.cp : L.cn, L.cls_pw);
+      }
       ly_loss_add(L.acc, LY_LOSS_CLS, sc);
     }
   }
@@ -181,25 +222,52 @@ __global__ __launch_bounds__(LY_THREADS) void ly_loss_apply_kernel(const LyLossL
   float* d = L.dp + cell * L.no;
 #pragma unroll
   for (int r = 0; r < 4; ++r) atomicAdd(d + r, scale * c[1 + r]);
-  if (L.winner[cell] == (int)idx) L.tobj[cell] = fmaxf(c[0], 0.f);
+  if (L.sort) {                                                            // sort_obj_iou: the cell's maximum (values >= 0: monotone as integers)
+    float v = fmaxf(c[0], 0.f);
+    if (L.gr < 1.f) v = (1.f - L.gr) + L.gr * v;
+    atomicMax(reinterpret_cast<int*>(L.tobj + cell), __float_as_int(v));
+  } else if (L.winner[cell] == (int)idx) {
+    if (L.gr < 1.f) L.tobj[cell] = (1.f - L.gr) + L.gr * fmaxf(c[0], 0.f);
+    else L.tobj[cell] = fmaxf(c[0], 0.f);
+  }
   const int nc = L.no - 5;
   if (nc > 1) {                                                            // d/dx of  cls * mean over (rows, classes) of BCE * bs
     const long t = idx % L.nt;
     const int cls = (int)L.targets[t * 6 + 1];
     const float cs = cls_gain * (float)L.bs / (L.acc[LY_LOSS_COUNT] * (float)nc);
     const float* pr = L.p + cell * L.no;
-    for (int q = 0; q < nc; ++q) atomicAdd(d + 5 + q, cs * ly_bce_grad(pr[5 + q], q == cls ? L.cp : L.cn, L.cls_pw));
+    if (L.gamma > 0.f) {
+      for (int q = 0; q < nc; ++q) {
+        float gq;
+        ly_focal(pr[5 + q], q == cls ? L.cp : L.cn, L.cls_pw, L.gamma, L.alpha, &gq);
+        atomicAdd(d + 5 + q, cs * gq);
+      }
+    } else {
+      for (int q = 0; q < nc; ++q) atomicAdd(d + 5 + q, cs * ly_bce_grad(pr[5 + q], q == cls ? L.cp : L.cn, L.cls_pw));
+    }
   }
 }
 
-__global__ __launch_bounds__(LY_THREADS) void ly_loss_obj_kernel(const LyLossLevel L, float obj_scale) {
+// balance_dev == NULL: obj_scale by value (host balance); else the level's entry of the device balance vector (autobalance), read before
+// ly_loss_finish updates it
+__global__ __launch_bounds__(LY_THREADS) void ly_loss_obj_kernel(const LyLossLevel L, float obj_scale, float obj_gain, const double* __restrict__ balance_dev,
+                                                                 int level) {
   __shared__ float red[4];
   const long cells = (long)L.bs * L.na * L.ny * L.nx;
+  if (balance_dev) obj_scale = obj_gain * (float)balance_dev[level] * (float)L.bs / (float)cells;
   float s = 0.f;
-  for (long i = (long)blockIdx.x * LY_THREADS + threadIdx.x; i < cells; i += (long)gridDim.x * LY_THREADS) {
-    const float x = L.p[i * L.no + 4], z = L.tobj[i];
-    s += ly_bce(x, z, L.obj_pw);
-    L.dp[i * L.no + 4] = ly_bce_grad(x, z, L.obj_pw) * obj_scale;          // obj_scale = obj * balance * bs / cells
+  if (L.gamma > 0.f) {
+    for (long i = (long)blockIdx.x * LY_THREADS + threadIdx.x; i < cells; i += (long)gridDim.x * LY_THREADS) {
+      float g;
+      s += ly_focal(L.p[i * L.no + 4], L.tobj[i], L.obj_pw, L.gamma, L.alpha, &g);
+      L.dp[i * L.no + 4] = g * obj_scale;
+    }
+  } else {
+    for (long i = (long)blockIdx.x * LY_THREADS + threadIdx.x; i < cells; i += (long)gridDim.x * LY_THREADS) {
+      const float x = L.p[i * L.no + 4], z = L.tobj[i];
+      s += ly_bce(x, z, L.obj_pw);
+      L.dp[i * L.no + 4] = ly_bce_grad(x, z, L.obj_pw) * obj_scale;          // obj_scale = obj * balance * bs / cells
+    }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
@@ -208,15 +276,18 @@ __global__ __launch_bounds__(LY_THREADS) void ly_loss_obj_kernel(const LyLossLev
   if (threadIdx.x == 0) ly_loss_add(L.acc, LY_LOSS_OBJ, red[0] + red[1] + red[2] + red[3]);
 }
 
-extern "C" int ly_loss_level(const float* p, float* dp, const float* anchors, const float* targets, int bs, int na, int ny, int nx, int no, long nt,
-                             float anchor_t, float box_gain, float obj_gain, float balance, float* tobj, int* winner, long* cand_cell, float* cand,
-                             float* acc, float* tbox, int match_only, float cls_gain, float cp, float cn, float cls_pw, float obj_pw, void* stream) {
+extern "C" int ly_loss_level_opts(const float* p, float* dp, const float* anchors, const float* targets, int bs, int na, int ny, int nx, int no, long nt,
+                                  float anchor_t, float box_gain, float obj_gain, float balance, float* tobj, int* winner, long* cand_cell, float* cand,
+                                  float* acc, float* tbox, int match_only, float cls_gain, float cp, float cn, float cls_pw, float obj_pw,
+                                  float fl_gamma, float fl_alpha, float gr, int sort_obj_iou, const double* balance_dev, int level, void* stream) {
+  LY_CHECK(fl_gamma >= 0.f && fl_alpha >= 0.f && fl_alpha <= 1.f && gr >= 0.f && gr <= 1.f, "loss_level: fl_gamma >= 0, fl_alpha and gr in [0, 1]");
+  LY_CHECK(!balance_dev || (level >= 0 && ((uintptr_t)balance_dev & 7) == 0), "loss_level: device balance needs its level index and 8-byte alignment");
   LY_CHECK(((uintptr_t)acc & 7) == 0, "loss_level: acc must be 8-byte aligned (64-bit integer atomics)");
   LY_CHECK(p && (dp || match_only) && anchors && tobj && winner && acc && (nt == 0 || (targets && cand_cell && cand)), "loss_level: null pointer");
   LY_CHECK(bs > 0 && na > 0 && ny > 0 && nx > 0 && no >= 5 && nt >= 0, "loss_level: bad sizes");
   const long cells = (long)bs * na * ny * nx;
   LY_CHECK(5L * na * nt < (1L << 31) && cells < (1L << 40), "loss_level: too many candidates");
-  LyLossLevel L{p, dp, anchors, targets, bs, na, ny, nx, no, nt, anchor_t, tobj, winner, cand_cell, cand, acc, tbox, cp, cn, cls_pw, obj_pw};
+  LyLossLevel L{p, dp, anchors, targets, bs, na, ny, nx, no, nt, anchor_t, tobj, winner, cand_cell, cand, acc, tbox, cp, cn, cls_pw, obj_pw, fl_gamma, fl_alpha, gr, sort_obj_iou != 0};
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const long ncand = 5L * na * nt;
   if (ncand > 0) {
@@ -230,14 +301,24 @@ extern "C" int ly_loss_level(const float* p, float* dp, const float* anchors, co
   }
   long ob = (cells + LY_THREADS * 8L - 1) / (LY_THREADS * 8L);
   ob = ob < 1 ? 1 : ob > 2048 ? 2048 : ob;
-  hipLaunchKernelGGL(ly_loss_obj_kernel, dim3((unsigned)ob), dim3(LY_THREADS), 0, st, L, obj_gain * balance * (float)bs / (float)cells);
+  hipLaunchKernelGGL(ly_loss_obj_kernel, dim3((unsigned)ob), dim3(LY_THREADS), 0, st, L, obj_gain * balance * (float)bs / (float)cells, obj_gain,
+                     balance_dev, level);
   LY_LAUNCH_CHECK();
   return 0;
 }
 
-// out[0] = total loss, out[1..3] = (lbox, lobj, lcls) as the reference returns them; acc = [nl][LY_LOSS_ACC] level accumulators
+extern "C" int ly_loss_level(const float* p, float* dp, const float* anchors, const float* targets, int bs, int na, int ny, int nx, int no, long nt,
+                             float anchor_t, float box_gain, float obj_gain, float balance, float* tobj, int* winner, long* cand_cell, float* cand,
+                             float* acc, float* tbox, int match_only, float cls_gain, float cp, float cn, float cls_pw, float obj_pw, void* stream) {
+  return ly_loss_level_opts(p, dp, anchors, targets, bs, na, ny, nx, no, nt, anchor_t, box_gain, obj_gain, balance, tobj, winner, cand_cell, cand, acc,
+                            tbox, match_only, cls_gain, cp, cn, cls_pw, obj_pw, 0.f, 0.25f, 1.f, 0, nullptr, 0, stream);
+}
+
+// out[0] = total loss, out[1..3] = (lbox, lobj, lcls) as the reference returns them; acc = [nl][LY_LOSS_ACC] level accumulators.
+// balance_dev != NULL (autobalance): lobj with the device vector's present values, then its update and normalisation in place
 __global__ void ly_loss_finish_kernel(const float* __restrict__ acc, int nl, const float* __restrict__ cells, const float* __restrict__ balance,
-                                      float box_gain, float obj_gain, float cls_gain, int nc, float bs, float* __restrict__ out) {
+                                      float box_gain, float obj_gain, float cls_gain, int nc, float bs, float* __restrict__ out,
+                                      double* __restrict__ balance_dev, int ssi) {
   if (threadIdx.x != 0) return;
   float lbox = 0.f, lobj = 0.f, lcls = 0.f, bad = 0.f;
   for (int i = 0; i < nl; ++i) {
@@ -248,7 +329,17 @@ __global__ void ly_loss_finish_kernel(const float* __restrict__ acc, int nl, con
       lbox += ly_loss_sum(a, LY_LOSS_BOX) / count;
       if (nc > 1) lcls += ly_loss_sum(a, LY_LOSS_CLS) / (count * (float)nc);
     }
-    lobj += ly_loss_sum(a, LY_LOSS_OBJ) / cells[i] * balance[i];
+    if (balance_dev) {
+      lobj += ly_loss_sum(a, LY_LOSS_OBJ) / cells[i] * (float)balance_dev[i];
+      const double obji = ((double)reinterpret_cast<const long long*>(a)[LY_LOSS_OBJ] * (1.0 / LY_LOSS_FIX) + (double)a[LY_LOSS_WILD + LY_LOSS_OBJ]) / (double)cells[i];
+      balance_dev[i] = balance_dev[i] * 0.9999 + 0.0001 / obji;              // utils/loss.py:178
+    } else {
+      lobj += ly_loss_sum(a, LY_LOSS_OBJ) / cells[i] * balance[i];
+    }
+  }
+  if (balance_dev) {                                                         // utils/loss.py:180-181
+    const double d = balance_dev[ssi];
+    for (int i = 0; i < nl; ++i) balance_dev[i] /= d;
   }
   lbox *= box_gain;
   lobj *= obj_gain;
@@ -259,11 +350,18 @@ __global__ void ly_loss_finish_kernel(const float* __restrict__ acc, int nl, con
   out[3] = lcls;
 }
 
-extern "C" int ly_loss_finish(const float* acc, int nl, const float* cells, const float* balance, float box_gain, float obj_gain, float cls_gain,
-                              int nc, int bs, float* out, void* stream) {
-  LY_CHECK(acc && cells && balance && out && nl > 0, "loss_finish: bad arguments");
+extern "C" int ly_loss_finish_opts(const float* acc, int nl, const float* cells, const float* balance, float box_gain, float obj_gain, float cls_gain,
+                                   int nc, int bs, float* out, double* balance_dev, int ssi, void* stream) {
+  LY_CHECK(acc && cells && (balance || balance_dev) && out && nl > 0, "loss_finish: bad arguments");
+  LY_CHECK(!balance_dev || (ssi >= 0 && ssi < nl && ((uintptr_t)balance_dev & 7) == 0), "loss_finish: device balance needs ssi in [0, nl) and 8-byte alignment");
   hipLaunchKernelGGL(ly_loss_finish_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), acc, nl, cells, balance, box_gain, obj_gain,
-                     cls_gain, nc, (float)bs, out);
+                     cls_gain, nc, (float)bs, out, balance_dev, ssi);
   LY_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int ly_loss_finish(const float* acc, int nl, const float* cells, const float* balance, float box_gain, float obj_gain, float cls_gain,
+                              int nc, int bs, float* out, void* stream) {
+  LY_CHECK(balance, "loss_finish: bad arguments");
+  return ly_loss_finish_opts(acc, nl, cells, balance, box_gain, obj_gain, cls_gain, nc, bs, out, nullptr, 0, stream);
 }

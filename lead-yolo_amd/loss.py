@@ -11,6 +11,9 @@ is outside the batch: the loss comes back NaN and `build_targets` raises IndexEr
 for a class >= nc and wraps a negative class -k to nc - k; rejecting negatives too is a deliberate difference (a negative class is a corrupt
 label).  A silently accepted row would train all its classes as negatives.  nc = 1 never reads the class column, and padding rows
 (image index -1) stay silent whatever their class column holds.
+The reference's remaining options run in the same kernels (csrc/ly_loss.hip, head of the file): focal loss on both BCEs
+(`hyp['fl_gamma'] > 0`, opt-in through `allow_focal=True`; alpha 0.25), `autobalance=True` (the balance vector is device state, updated
+by every call without a host sync), and the attributes `gr` and `sort_obj_iou`, read at call time.
 `build_targets` is the inspectable view of the kernel's anchor matching: it runs the matching kernel alone and reads its candidate buffers back (int64 indices bit-exact with the reference's vectors, tests/test_loss.py).
 """
 import torch
@@ -22,18 +25,54 @@ DEFAULT_HYP = dict(box=0.05, cls=0.5, cls_pw=1.0, obj=1.0, obj_pw=1.0, anchor_t=
 
 
 class ComputeLoss:
-    sort_obj_iou = False
+    """The reference's `ComputeLoss(model, autobalance=False)` on the device.
 
-    def __init__(self, model, autobalance=False, hyp=None):
+    hyp['fl_gamma'] > 0 asks for focal loss on the objectness and class BCEs (utils/loss.py:104-108, alpha = 0.25).  It is opt-in:
+    without `allow_focal=True` a positive fl_gamma raises NotImplementedError, so that a hyper-parameter file that merely carries the key
+    does not change the loss silently.  `gr` (objectness target (1 - gr) + gr * iou, in [0, 1]) and `sort_obj_iou` (a cell shared by several
+    targets keeps their largest iou instead of the last one's) are attributes read at every call, as the reference's are.
+
+    autobalance=True needs `det.stride` to contain 16 (the reference normalises by that level's balance).  The balance vector then lives on
+    the device (float64) and EVERY call updates it — calls under no_grad and calls from `validate(compute_loss=...)` included, which is what
+    the reference does when the same object is handed to val.py; a captured step updates it at every replay.  `.balance` reads it back
+    (one host sync: an inspection path) and assigning `.balance` writes it in place."""
+    sort_obj_iou = False
+    FL_ALPHA = 0.25            # FocalLoss's default alpha; the reference never passes another
+
+    def __init__(self, model, autobalance=False, hyp=None, allow_focal=False):
         det = model.model[-1] if hasattr(model, "model") else model
         self.hyp = dict(DEFAULT_HYP, **(hyp or getattr(model, "hyp", None) or {}))
-        if self.hyp["fl_gamma"] > 0 or autobalance:
-            raise NotImplementedError("focal loss / autobalance are not used by the LEAD-YOLO recipe and are not built")
+        if self.hyp["fl_gamma"] > 0 and not allow_focal:
+            raise NotImplementedError(f"hyp['fl_gamma'] = {self.hyp['fl_gamma']}: focal loss is opt-in here — pass ComputeLoss(..., allow_focal=True) "
+                                      "to use it (alpha 0.25, on the objectness and class BCEs), or set fl_gamma to 0")
+        self.gamma = float(self.hyp["fl_gamma"]) if self.hyp["fl_gamma"] > 0 else 0.0
         self.na, self.nc, self.nl = det.na, det.nc, det.nl
         self.cp, self.cn = 1.0 - 0.5 * self.hyp["label_smoothing"], 0.5 * self.hyp["label_smoothing"]      # smooth_BCE (utils/loss.py:17-19)
         self.anchors = det.anchors
-        self.balance = {3: [4.0, 1.0, 0.4]}.get(self.nl, [4.0, 1.0, 0.25, 0.06, 0.02])
+        self._balance = {3: [4.0, 1.0, 0.4]}.get(self.nl, [4.0, 1.0, 0.25, 0.06, 0.02])[:self.nl]
+        self.autobalance, self.ssi = bool(autobalance), 0
+        if self.autobalance:
+            strides = [float(s) for s in det.stride] if getattr(det, "stride", None) is not None else []
+            if 16.0 not in strides:
+                raise ValueError("ComputeLoss(autobalance=True): the balance vector is normalised by the entry of the stride-16 level "
+                                 f"(utils/loss.py:111,181), and the detection head's strides are {strides or 'not set'}")
+            self.ssi = strides.index(16.0)
+        self._bal_dev = {}            # device -> float64 [nl]: the autobalanced vector (persistent state; captured steps address it)
         self.gr = 1.0
+        self._const = {}
+
+    @property
+    def balance(self):
+        """the level weights of the objectness loss; with autobalance the device vector read back (one host sync)"""
+        if self.autobalance and self._bal_dev:
+            return next(iter(self._bal_dev.values())).tolist()
+        return self._balance
+
+    @balance.setter
+    def balance(self, value):
+        self._balance = [float(v) for v in value]
+        for t in self._bal_dev.values():                  # in place: captured steps keep addressing the same memory
+            t.copy_(torch.tensor(self._balance[:t.numel()], dtype=torch.float64))
         self._const = {}
 
     # ---- shared plumbing -----------------------------------------------------------------------------------------
@@ -50,8 +89,12 @@ class ComputeLoss:
         key = (tuple(cells), self.anchors._version)      # the float32 anchors may be a COPY of the buffer (bf16 model, other device): an
         if k is None or k["cells_key"] != key:            # in-place write to it (anchors.check_anchors) bumps its version
             k = dict(cells=torch.tensor([float(c) for c in cells], device=device),
-                     balance=torch.tensor([float(b) for b in self.balance[:len(cells)]], device=device),
+                     balance=torch.tensor([float(b) for b in self._balance[:len(cells)]], device=device),
                      anchors=[self.anchors[i].to(device).float().contiguous() for i in range(self.nl)], cells_key=key)
+            if self.autobalance:
+                if device not in self._bal_dev:
+                    self._bal_dev[device] = torch.tensor(self._balance[:len(cells)], dtype=torch.float64, device=device)
+                k["bal"] = self._bal_dev[device]          # the same tensor in every rebuilt dict: GraphedTrainStep pins these dicts
             self._const[device] = k
         return k
 
@@ -63,6 +106,10 @@ class ComputeLoss:
         bs = preds[0].shape[0]
         cells = [int(p.shape[0] * p.shape[1] * p.shape[2] * p.shape[3]) for p in preds]
         k = self._consts(dev, cells)
+        gr, sort = float(self.gr), bool(self.sort_obj_iou)
+        if not 0.0 <= gr <= 1.0:
+            raise ValueError(f"ComputeLoss: gr must be in [0, 1] (objectness target (1 - gr) + gr * iou), got {self.gr}")
+        bal = capi.ptr(k.get("bal"))
         ncand = max(5 * na * nt, 1)
         at = (sum(cells) + 1) // 2 * 2                                                       # the accumulators hold int64 sums: 8-byte aligned
         zero = ops.zeros_f32(at + ACC * nl, dev)                                             # tobj of every level + accumulators (step pool)
@@ -76,12 +123,12 @@ class ComputeLoss:
         for i, p in enumerate(preds):
             dp = None if match_only else ops.zeros_f32(p.numel(), dev).view(p.shape)      # read by the backward of the same step only
             _, _, ny, nx, no = p.shape
-            capi.check(capi.lib().ly_loss_level(capi.ptr(p), capi.ptr(dp), capi.ptr(k["anchors"][i]), capi.ptr(targets), bs, na, ny, nx, no, nt,
-                                                float(self.hyp["anchor_t"]), float(self.hyp["box"]), float(self.hyp["obj"]), float(self.balance[i]),
-                                                capi.ptr(zero[off:off + cells[i]]), capi.ptr(winner[off:off + cells[i]]), capi.ptr(cand_cell[i]),
-                                                capi.ptr(cand[i]), capi.ptr(acc[i]), capi.ptr(tbox[i]) if match_only else capi.ptr(None),
-                                                int(match_only), float(self.hyp["cls"]), float(self.cp), float(self.cn), float(self.hyp["cls_pw"]),
-                                                float(self.hyp["obj_pw"]), st), "ly_loss_level")
+            capi.check(capi.lib().ly_loss_level_opts(capi.ptr(p), capi.ptr(dp), capi.ptr(k["anchors"][i]), capi.ptr(targets), bs, na, ny, nx, no, nt,
+                                                     float(self.hyp["anchor_t"]), float(self.hyp["box"]), float(self.hyp["obj"]), float(self._balance[i]),
+                                                     capi.ptr(zero[off:off + cells[i]]), capi.ptr(winner[off:off + cells[i]]), capi.ptr(cand_cell[i]),
+                                                     capi.ptr(cand[i]), capi.ptr(acc[i]), capi.ptr(tbox[i]) if match_only else capi.ptr(None),
+                                                     int(match_only), float(self.hyp["cls"]), float(self.cp), float(self.cn), float(self.hyp["cls_pw"]),
+                                                     float(self.hyp["obj_pw"]), self.gamma, self.FL_ALPHA, gr, int(sort), bal, i, st), "ly_loss_level_opts")
             dps.append(dp)
             off += cells[i]
         return dict(dps=dps, acc=acc, cand_cell=cand_cell, tbox=tbox, k=k, bs=bs, nt=nt)
@@ -122,8 +169,6 @@ class ComputeLoss:
 
     def __call__(self, p, targets):
         targets = self._check(p, targets)
-        if self.gr != 1.0 or self.sort_obj_iou:
-            raise NotImplementedError("device loss: gr != 1 / sort_obj_iou are not built")
         loss, out = _LossFn.apply(self, targets, *p)
         return loss, out[1:4].detach()
 
@@ -135,9 +180,9 @@ class _LossFn(torch.autograd.Function):
         preds = [p.float().contiguous() for p in preds]                     # bf16 / fp16 heads: the loss itself is fp32 (as under autocast)
         r = cl._levels(preds, targets, match_only=False)
         out = torch.empty(4, dtype=torch.float32, device=preds[0].device)
-        capi.check(capi.lib().ly_loss_finish(capi.ptr(r["acc"]), len(preds), capi.ptr(r["k"]["cells"]), capi.ptr(r["k"]["balance"]),
-                                             float(cl.hyp["box"]), float(cl.hyp["obj"]), float(cl.hyp["cls"]), int(cl.nc), r["bs"], capi.ptr(out),
-                                             capi.stream_ptr()), "ly_loss_finish")
+        capi.check(capi.lib().ly_loss_finish_opts(capi.ptr(r["acc"]), len(preds), capi.ptr(r["k"]["cells"]), capi.ptr(r["k"]["balance"]),
+                                                  float(cl.hyp["box"]), float(cl.hyp["obj"]), float(cl.hyp["cls"]), int(cl.nc), r["bs"], capi.ptr(out),
+                                                  capi.ptr(r["k"].get("bal")), int(cl.ssi), capi.stream_ptr()), "ly_loss_finish_opts")
         ctx.save_for_backward(*r["dps"])
         ctx.mark_non_differentiable(out)
         return out[:1].clone(), out

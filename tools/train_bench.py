@@ -1,6 +1,8 @@
 """Times the full training step (forward, loss, backward, clip, optimiser) of lead-yolo-s on synthetic COCO-shaped data.
 
     --optimizer SGD | Adam | AdamW, or a comma list (e.g. SGD,AdamW): one model per optimiser, timed in alternating rounds
+    --fl-gamma G / --autobalance: the loss options (focal loss on both BCEs, device-resident autobalance); a name may carry them per leg as
+      NAME+focal (fl_gamma 1.5 and autobalance), e.g. --optimizer SGD,SGD+focal times both settings in alternating rounds of one process
     --graphed: the captured step (train.GraphedTrainStep with ModelEMA), as bench.py times it; --dtype bf16: autocast bf16"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,6 +20,8 @@ ap.add_argument("--optimizer", default="SGD")
 ap.add_argument("--graphed", action="store_true")
 ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32")
 ap.add_argument("--rounds", type=int, default=1, help="alternating timed rounds of --steps steps per optimiser")
+ap.add_argument("--fl-gamma", type=float, default=0.0, help="focal loss gamma (0: plain BCE)")
+ap.add_argument("--autobalance", action="store_true")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 amp = torch.bfloat16 if a.dtype == "bf16" else None
@@ -29,10 +33,12 @@ tg = torch.cat((torch.sort(torch.randint(0, a.bs, (nb, 1), generator=g).float(),
 
 
 def make(name):
+    name, _, leg = name.partition("+")
+    gamma, auto = (1.5, True) if leg == "focal" else (a.fl_gamma, a.autobalance)
     torch.manual_seed(0)
     m = L.Model(L.load_cfg(scale=a.scale)).to(dev).train()
     opt = L.smart_optimizer(m, name, 0.01 if name == "SGD" else 1e-3, 0.937, 5e-4 * a.bs / 64)
-    cl = L.ComputeLoss(m)
+    cl = L.ComputeLoss(m, autobalance=auto, hyp=dict(fl_gamma=gamma), allow_focal=True)
     if a.fwd_only:
         def step():
             with torch.no_grad():
