@@ -15,6 +15,7 @@ Only [C]-sized vectors are handled with torch ops (coefficients of step 3, param
 """
 import collections
 import ctypes
+import functools
 
 import os
 
@@ -117,6 +118,16 @@ def _conv_forward(spec, x0, x1, wp, e_scale, e_shift, act, stats=None, store=Fal
     return out
 
 
+def _bn_bwd_coeffs(gamma, beta, sums, ch, count, a, mean, invstd, train, transpose=None):
+    """ops.bn_bwd_coeffs with the destination of dgamma / dbeta decided (ops.ParamGrad; gamma / beta: the BatchNorm parameters, or None):
+    added into the sink's storage and None, None in their place, else fresh for autograd -> (dgamma, dbeta, alpha, kappa, lambda).
+    transpose = (t, c): fresh values come back as views in the parameters' [c][t] order."""
+    g = ops.ParamGrad(gamma, beta, accept=ops.CONTIGUOUS, view=None if transpose is None else lambda v: v.view(transpose).t())
+    dgamma, dbeta, alpha, kappa, lam = ops.bn_bwd_coeffs(sums, ch, count, a, mean, invstd, train, dgamma=g.targets[0], dbeta=g.targets[1],
+                                                         transpose=transpose)
+    return (*g.finish(dgamma, dbeta), alpha, kappa, lam)
+
+
 def affine_backward(dy, u, a, b, act, mean, invstd, train, inplace=True, gamma=None, beta=None, lddy=None, out=None):
     """du and (dgamma, dbeta) for v = a*u + b, y = act(v); dy/u are NHWC-dense [n, c, h, w].  du is written over u unless
     inplace=False (u is a tensor saved for backward) or into `out` (e.g. dy itself).  gamma / beta: the BatchNorm parameters — when a gradient sink holds their
@@ -125,13 +136,7 @@ def affine_backward(dy, u, a, b, act, mean, invstd, train, inplace=True, gamma=N
     rows = n * h * w
     lddy = c if lddy is None else lddy          # dy may be a channel slice of a wider gradient (row stride lddy), read in place
     sums = ops.bnact_bwd_reduce(dy, lddy, u, c, rows, c, a, b, act)
-    tg, tb = ops.grad_target(gamma), ops.grad_target(beta)
-    direct = tg is not None and tb is not None and tg.numel() == c and tb.numel() == c
-    dgamma, dbeta, alpha, kappa, lam = ops.bn_bwd_coeffs(sums, c, rows, a, mean, invstd, train, dgamma=tg if direct else None,
-                                                         dbeta=tb if direct else None)
-    if direct:
-        ops.grad_done(gamma)
-        ops.grad_done(beta)
+    dgamma, dbeta, alpha, kappa, lam = _bn_bwd_coeffs(gamma, beta, sums, c, rows, a, mean, invstd, train)
     du = out if out is not None else u if inplace else torch.empty_like(u)     # out: e.g. dy itself (elementwise: same index read and written)
     ops.bnact_bwd_apply(dy, lddy, u, c, rows, c, a, b, act, alpha, kappa, lam, du, c)
     return du, dgamma, dbeta
@@ -145,8 +150,8 @@ def conv_wgrad(spec, du, x0, x1, weight):
     n, co, ho, wo = du.shape
     m = n * ho * wo
     nv = weight.shape[0]
-    tgt = ops.grad_target(weight)
-    dw = tgt if tgt is not None else torch.zeros(weight.shape, dtype=torch.float32, device=du.device)
+    g = ops.ParamGrad(weight)
+    dw = g.buf
     if spec.kind == "pw":
         # two row sources (a concat read in place): one launch when both are plain rows
         ops.wgrad_group(_pw_wgrad_problems(du, co, 0, co, _source(spec, x0, x1), dw, n_valid=nv))
@@ -155,7 +160,7 @@ def conv_wgrad(spec, du, x0, x1, weight):
         c = t0.shape[1]
         # tap-major gradient storage (optim.FusedSGD, [cout][tap][cin]): packed rows, contiguous atomics; the weight's own layout
         # [cout][cin][tap] otherwise (lanes 36 bytes apart: ~3x slower atomics)
-        ts, cs = (c, 1) if _tap_major(dw) else (1, 9)
+        ts, cs = (c, 1) if ops.tap_major(dw) else (1, 9)
         ops.wgrad(M=m, H=ho, W=wo, N=co, du=du, lddu=co, x=t0, ldx=ld0, Hin=ho, Win=wo, Cin=c, dw=dw, lddw=9 * c, ks=3, stride=1, pad=1,
                   dw_ts=ts, dw_cs=cs, n_valid=nv)
     else:
@@ -170,10 +175,7 @@ def conv_wgrad(spec, du, x0, x1, weight):
             if u8 and k == 4 and co == nv and dw.is_contiguous() and ops.patch4_wgrad_u8_ok(x0, du, co):
                 # round 6: straight from the image — no space-to-depth rows (157 MB written and read back at bs = 64), no scratch, no add
                 ops.patch4_wgrad_u8(x0, du, co, co, dw, 1.0 / 255.0)
-                if tgt is not None:
-                    ops.grad_done(weight)
-                    return None
-                return dw
+                return g.finish()
             if u8 and k == 4 and x0.is_contiguous():
                 xr = ops.patch4_rows_u8(x0, du.dtype)                # one pass (was a permuted copy + a cast)
             else:
@@ -190,13 +192,10 @@ def conv_wgrad(spec, du, x0, x1, weight):
                       dw_ts=1, dw_cs=k * k, n_valid=nv)
         else:
             xr = _rows_dense(x0)
-            ts, cs = (c, 1) if _tap_major(dw) else (1, k * k)
+            ts, cs = (c, 1) if ops.tap_major(dw) else (1, k * k)
             ops.wgrad(M=m, H=ho, W=wo, N=co, du=du, lddu=co, x=xr, ldx=c, Hin=h, Win=w, Cin=c, dw=dw, lddw=k * k * c, ks=k, stride=k,
                       dw_ts=ts, dw_cs=cs, n_valid=nv)
-    if tgt is not None:
-        ops.grad_done(weight)
-        return None
-    return dw
+    return g.finish()
 
 
 def _pw_wgrad_problems(du, lddu, du_off, N, src, dw, n_valid=None, dup=None):
@@ -226,22 +225,6 @@ def _pw_dgrad(du, wt, kin, c0, up, need0, need1):
     if need0:
         d0 = ops.up2_bwd(d, kin, n, ho // 2, wo // 2, c0) if up else d if c0 == kin else d[:, :c0]
     return d0, (d[:, c0:] if need1 and c0 < kin else None)
-
-
-def _tap_major_rows(g):
-    """[co, kh*kw*ci] row view of the [co][kh][kw][ci] storage behind a tap-major gradient target (see _tap_major), else None"""
-    if g is None or not _tap_major(g):
-        return None
-    co, ci, kh, kw = g.shape
-    rows = g.permute(0, 2, 3, 1)
-    if not rows.is_contiguous():                 # (reshape would hand out a copy: the gradient written into it would be lost)
-        return None
-    return rows.view(co, kh * kw * ci)
-
-
-def _tap_major(g):
-    """gradient tensor of a [co, ci, kh, kw] weight whose storage is [co][kh][kw][ci] (see optim.FusedSGD)"""
-    return g.dim() == 4 and not g.is_contiguous() and g.stride(1) == 1 and g.stride(3) == g.shape[1]
 
 
 def conv_dgrad(spec, du, weight, x0, x1, need0, need1, slots=(None, None)):
@@ -352,7 +335,7 @@ class ConvBnAct(torch.autograd.Function):
                     if spec.bn is None:
                         dbias, dgamma, dbeta = dbeta, None, None
                     elif spec.bn_train:
-                        dbias = torch.zeros_like(bias_f)                               # BN removes the batch mean: d/dbias = 0
+                        dbias = ops.zero_bias_grad(bias_f)          # (always zeros for autograd, whatever the sink holds)
                     else:
                         dbias = a * (dbeta if dbeta is not None else b_param.grad)
                 elif spec.bn is None:
@@ -451,9 +434,9 @@ class ConvBnActPair(torch.autograd.Function):
             src = _source(spec, x0, x1)
             c0, kin = src.k0, src.shape[1]
             # the two weight gradients as ONE stacked [2c_, kin] matrix when the sink keeps them adjacent (optim.FusedSGD does)
-            tw = [ops.grad_target(ctx.params[i][0]) for i in range(2)]
-            stacked = (need[6] and need[7] and tw[0] is not None and tw[1] is not None and tw[0].is_contiguous() and tw[1].is_contiguous()
-                       and tw[1].data_ptr() == tw[0].data_ptr() + 4 * tw[0].numel())
+            gw = [ops.ParamGrad(ctx.params[i][0]) for i in range(2)]
+            stacked = (need[6] and need[7] and gw[0].direct and gw[1].direct and gw[0].buf.is_contiguous() and gw[1].buf.is_contiguous()
+                       and gw[1].buf.data_ptr() == gw[0].buf.data_ptr() + 4 * gw[0].buf.numel())
             dys = []
             for dy in (dy1, dy2):
                 if dy is None:
@@ -465,22 +448,12 @@ class ConvBnActPair(torch.autograd.Function):
             sums2 = ops.bnact_bwd_reduce_pair(dya, lda, dyb, ldb, c_, u, co, rows, co, v[0], v[1], spec.act)
             coef = torch.empty(3, co, dtype=torch.float32, device=u.device)
             # the coefficient kernel of both units in ONE launch; the gradients of gamma / beta are added into the sink's storage where
-            # there is one, else into fresh zeros handed to autograd
-            tgt, fresh = [], None
-            for i in range(2):
-                w_p, g_p, b_p = ctx.params[i]
-                tg, tb = ops.grad_target(g_p), ops.grad_target(b_p)
-                if tg is not None and tb is not None and tg.is_contiguous() and tb.is_contiguous():
-                    tgt.append((tg, tb))
-                else:
-                    fresh = torch.zeros(2, 2, c_, dtype=torch.float32, device=u.device) if fresh is None else fresh
-                    tgt.append((fresh[i, 0], fresh[i, 1]))
-                    out[8 + 2 * i], out[9 + 2 * i] = fresh[i, 0], fresh[i, 1]
-            ops.bn_bwd_coeffs_pair(sums2[0], sums2[1], c_, rows, v, tgt, coef)
-            for i in range(2):
-                if out[8 + 2 * i] is None:
-                    ops.grad_done(ctx.params[i][1])
-                    ops.grad_done(ctx.params[i][2])
+            # there is one, else into fresh zeros handed to autograd (ONE fill for both units, made when the first of them needs it)
+            fill = functools.lru_cache(None)(lambda: torch.zeros(2, 2, c_, dtype=torch.float32, device=u.device))
+            gbn = [ops.ParamGrad(g_p, b_p, accept=ops.CONTIGUOUS, fresh=lambda i=i: tuple(fill()[i])) for i, (_, g_p, b_p) in enumerate(ctx.params)]
+            ops.bn_bwd_coeffs_pair(sums2[0], sums2[1], c_, rows, v, [g.bufs for g in gbn], coef)
+            for i, g in enumerate(gbn):
+                out[8 + 2 * i], out[9 + 2 * i] = g.finish()
             ops.bnact_bwd_apply_pair(dya, lda, dyb, ldb, c_, u, co, rows, co, v[0], v[1], spec.act, coef[0], coef[1], coef[2], du, co)
             # A lazily 2x-upsampled source: the adjoint of the upsample (sum over each 2x2 block) commutes with the 1x1 convolution, so it is
             # applied ONCE to du (co channels) and that source's weight and data gradients are plain contractions at a quarter of the rows —
@@ -489,20 +462,14 @@ class ConvBnActPair(torch.autograd.Function):
             dup = ops.up2_bwd(du, co, n, hq, wq, co) if spec.up else None
             for i in range(2):
                 off = i * c_
-                w_p = ctx.params[i][0]
                 if need[6 + i] and not stacked:
-                    tgt = tw[i]
-                    dw = tgt if tgt is not None else torch.zeros(w_p.shape, dtype=torch.float32, device=u.device)
-                    for q in _pw_wgrad_problems(du, co, off, c_, src, dw, dup=dup):
+                    for q in _pw_wgrad_problems(du, co, off, c_, src, gw[i].buf, dup=dup):
                         ops.wgrad(**q)
-                    if tgt is not None:
-                        ops.grad_done(w_p)
-                    else:
-                        out[6 + i] = dw
+                    out[6 + i] = gw[i].finish()
             if stacked:
-                ops.wgrad_group(_pw_wgrad_problems(du, co, 0, co, src, tw[0], dup=dup))
-                ops.grad_done(ctx.params[0][0])
-                ops.grad_done(ctx.params[1][0])
+                ops.wgrad_group(_pw_wgrad_problems(du, co, 0, co, src, gw[0].buf, dup=dup))
+                gw[0].finish()
+                gw[1].finish()
             s0, s1 = ctx.slots
             if ctx.split:
                 pl = ops.planes_of(du)
@@ -659,12 +626,8 @@ class MlpBlockFn(torch.autograd.Function):
             # second 1x1
             dh = ops.empty_nhwc(n, 2 * c, h, w, x)
             ops.gemm(M=m, H=h, W=w, K=c, N=2 * c, a0=dy, lda0=c, k0=c, wp=pack.packed(pack.src_matrix(p_w2, 2 * c, c, sr=1, sk=2 * c), c, pl), out=dh, ldo=2 * c)
-            def sink(p):
-                """(gradient tensor to add into, whether it is the parameter's own storage)"""
-                t = ops.grad_target(p)
-                return (t, True) if t is not None else (torch.zeros(p.shape, dtype=torch.float32, device=x.device), False)
-            dw2, d2 = sink(p_w2)
-            wg2 = dict(M=m, H=h, W=w, N=c, du=dy, lddu=c, x=u1 if pro else hid, ldx=2 * c, Hin=h, Win=w, Cin=2 * c, dw=dw2, lddw=2 * c,
+            g2 = ops.ParamGrad(p_w2)
+            wg2 = dict(M=m, H=h, W=w, N=c, du=dy, lddu=c, x=u1 if pro else hid, ldx=2 * c, Hin=h, Win=w, Cin=2 * c, dw=g2.buf, lddw=2 * c,
                        x_scale=a if pro else None, x_shift=b if pro else None)
             # BN + ReLU (with the prologue du1 is written over dh: u1 is still read by the weight gradient above, launched with the first
             # 1x1's below)
@@ -672,15 +635,16 @@ class MlpBlockFn(torch.autograd.Function):
             # first 1x1
             g = ops.empty_nhwc(n, c, h, w, x)
             ops.gemm(M=m, H=h, W=w, K=2 * c, N=c, a0=du1, lda0=2 * c, k0=2 * c, wp=pack.packed(pack.src_matrix(p_w1, c, 2 * c, sr=1, sk=c), 2 * c, pl), out=g, ldo=c)
-            dw1, d1 = sink(p_w1)
+            g1 = ops.ParamGrad(p_w1)
             # both 1x1 weight gradients in one launch (they share the launch's blocks: longer pixel chunks, half the tile flushes per pixel)
-            ops.wgrad_group([wg2, dict(M=m, H=h, W=w, N=2 * c, du=du1, lddu=2 * c, x=z, ldx=c, Hin=h, Win=w, Cin=c, dw=dw1, lddw=c)])
+            ops.wgrad_group([wg2, dict(M=m, H=h, W=w, N=2 * c, du=du1, lddu=2 * c, x=z, ldx=c, Hin=h, Win=w, Cin=c, dw=g1.buf, lddw=c)])
             # partial 3x3 conv on the first C/4 channels
             # channel counts padded to multiples of 4 (C/4 = 6, 10): the tiled wgrad then applies; the extra rows / columns
             # (gradients of, and against, the neighbouring untouched channels) are computed and discarded
             # written in the weight's own [c4][c4][3][3] layout; the padded rows / channels are masked off by n_valid / c_valid
-            dwp, dp = sink(p_wpc)
-            ts, cs = (c4, 1) if _tap_major(dwp) else (1, 9)
+            gp = ops.ParamGrad(p_wpc)
+            dwp = gp.buf
+            ts, cs = (c4, 1) if ops.tap_major(dwp) else (1, 9)
             ops.wgrad(M=m, H=h, W=w, N=c4p, du=g, lddu=c, x=x, ldx=c, Hin=h, Win=w, Cin=c4p, dw=dwp, lddw=9 * c4, ks=3, stride=1, pad=1,
                       dw_ts=ts, dw_cs=cs, n_valid=c4, c_valid=c4)
             dx = torch.empty_like(dy)                      # dy + g, the partial conv's channels dy + t
@@ -698,10 +662,8 @@ class MlpBlockFn(torch.autograd.Function):
                 ops.conv3x3(M=m, H=h, W=w, Cin=c4p, N=c4, x=g, ldx=c, wp=wt, out=t, ldo=c4p)
                 _lib().check(_lib().lib().ly_mlp_dx(_lib().ptr(dy), _lib().ptr(g), _lib().ptr(t), c4p, m, c, c4, _lib().ptr(dx), _lib().dtype_code(dy),
                                                     _lib().stream_ptr()), "ly_mlp_dx")
-            for prm, direct in ((p_wpc, dp), (p_w1, d1), (p_w2, d2)):
-                if direct:
-                    ops.grad_done(prm)
-        return (None, dx, None if dp else dwp, None if d1 else dw1, dgamma, dbeta, None if d2 else dw2)
+            dwp, dw1, dw2 = gp.finish(), g1.finish(), g2.finish()
+        return None, dx, dwp, dw1, dgamma, dbeta, dw2
 
 
 def _mlpblock_backward_fused(ctx, dy):
@@ -722,36 +684,23 @@ def _mlpblock_backward_fused(ctx, dy):
     # pass 1: s1 = sum dv, s2 = sum dv u
     sums = ops.new_stats(2 * c, x.device)
     ops.mlpblock_bwd(x, dy, n, h, w, c, pk_p, pk_1, pk_2t, pk_1t, a, b, stats=sums)
-    tg, tb = ops.grad_target(p_gamma), ops.grad_target(p_beta)
-    direct = tg is not None and tb is not None and tg.numel() == 2 * c and tb.numel() == 2 * c
-    dgamma, dbeta, alpha, kappa, lam = ops.bn_bwd_coeffs(sums, 2 * c, m, a, mean, invstd, True, dgamma=tg if direct else None,
-                                                         dbeta=tb if direct else None)
-    if direct:
-        ops.grad_done(p_gamma)
-        ops.grad_done(p_beta)
-
-    def sink(p):
-        t = ops.grad_target(p)
-        return (t, True) if t is not None and t.is_contiguous() else (torch.zeros(p.shape, dtype=torch.float32, device=x.device), False)
-    dw1, d1 = sink(p_w1)
-    dw2, d2 = sink(p_w2)
+    dgamma, dbeta, alpha, kappa, lam = _bn_bwd_coeffs(p_gamma, p_beta, sums, 2 * c, m, a, mean, invstd, True)
+    g1, g2 = ops.ParamGrad(p_w1, accept=ops.CONTIGUOUS), ops.ParamGrad(p_w2, accept=ops.CONTIGUOUS)      # ly_mlpblock_bwd writes plain [2c, c] / [c, 2c] rows
     # pass 2: g, dW1, dW2
     g = ops.empty_nhwc(n, c, h, w, x)
-    ops.mlpblock_bwd(x, dy, n, h, w, c, pk_p, pk_1, pk_2t, pk_1t, a, b, g=g, alpha=alpha, kappa=kappa, lam=lam, dw1=dw1, dw2=dw2)
+    ops.mlpblock_bwd(x, dy, n, h, w, c, pk_p, pk_1, pk_2t, pk_1t, a, b, g=g, alpha=alpha, kappa=kappa, lam=lam, dw1=g1.buf, dw2=g2.buf)
     # partial 3x3 conv on the first C/4 channels: weight gradient from (g, x), data gradient folded into dx = dy + [conv^T(g[:C/4]) | g[C/4:]]
-    tgt = ops.grad_target(p_wpc)
-    dwp, dp = (tgt, True) if tgt is not None else (torch.zeros(p_wpc.shape, dtype=torch.float32, device=x.device), False)
-    ts, cs = (c4, 1) if _tap_major(dwp) else (1, 9)
+    gp = ops.ParamGrad(p_wpc)
+    dwp = gp.buf
+    ts, cs = (c4, 1) if ops.tap_major(dwp) else (1, 9)
     wt = pack.packed(pack.src_taps(p_wpc, c4p, transposed_flipped=True), 9 * c4p, pl)
     # the tail in ONE launch: dx = dy + [conv^T(g[:C/4]) | g[C/4:]] and the partial conv's weight gradient out of the same patches
     dx, wdone = ops.mlpblock_bwd_dx(g, dy, x, n, h, w, c, wt, dwp=dwp, lddw=9 * c4, dw_ts=ts, dw_cs=cs)
     if not wdone:
         ops.wgrad(M=m, H=h, W=w, N=c4p, du=g, lddu=c, x=x, ldx=c, Hin=h, Win=w, Cin=c4p, dw=dwp, lddw=9 * c4, ks=3, stride=1, pad=1,
                   dw_ts=ts, dw_cs=cs, n_valid=c4, c_valid=c4)
-    for prm, direct_ in ((p_wpc, dp), (p_w1, d1), (p_w2, d2)):
-        if direct_:
-            ops.grad_done(prm)
-    return (None, dx, None if dp else dwp, None if d1 else dw1, dgamma, dbeta, None if d2 else dw2)
+    dwp, dw1, dw2 = gp.finish(), g1.finish(), g2.finish()
+    return None, dx, dwp, dw1, dgamma, dbeta, dw2
 
 
 MlpBlockFn._backward_fused = staticmethod(_mlpblock_backward_fused)
@@ -792,43 +741,15 @@ class CoordAttFn(torch.autograd.Function):
         w1, b1, gamma, beta, wh, bh, ww, bw = ctx.params
         dr, ldd = ops.rows(dout if dout.dtype == xr.dtype else dout.to(xr.dtype))          # a channel slice of a wider gradient: read in place
         dx, da_h, da_w = ops.coordatt_gate_bwd(dr, xr, ld, n, h, w, c, a_h, a_w, ldd=ldd)
-        targets, ret = [], []
-        for i, p in enumerate(ctx.params):                    # accumulate into the persistent gradient storage where there is one
-            if i == 1:                                        # conv1.bias: bn1 removes the batch mean, d/dbias == 0 (nothing to add)
-                sunk = p.requires_grad and ops.grad_target(p) is not None
-                ret.append(None if (sunk or not p.requires_grad) else torch.zeros_like(p))
-                continue
-            tgt = ops.grad_target(p) if p.requires_grad else None
-            fresh = tgt is None
-            if fresh:
-                tgt = torch.zeros(p.shape, dtype=torch.float32, device=xr.device)
-            targets.append(tgt)
-            ret.append(tgt if (fresh and p.requires_grad) else None)
-        # every target in the sink: accumulate in float64 scratches, rounded into the sink when the backward pass ends (ops.small_grad_scratch)
-        defer = ops.small_grads_ok() and all(r is None for r in ret) and all(t.is_contiguous() for t in targets)
-        no_sink = all(q is None or not q.requires_grad or ops.grad_target(q) is None for i, q in enumerate(ctx.params) if i != 1)
-        fresh64 = (not defer) and ops.DETERMINISTIC_SMALL_GRADS and no_sink
-        if defer:
-            targets = [ops.small_grad_scratch(t, q) for t, q in zip(targets, [q for i, q in enumerate(ctx.params) if i != 1])]
-        elif fresh64:                                         # no sink anywhere: float64 scratches, rounded right after the launch
-            shapes = [t.shape for t in targets]
-            targets = [ops.zeros_f64(t.numel(), xr.device) for t in targets]
+        # the seven small gradients take one route together (ly_coordatt_mlp_bwd has one float64 flag); conv1.bias (index 1) gets none: bn1
+        # removes the batch mean, d/dbias == 0
+        grads = ops.SmallGrad.group(ctx.params, zero=(1,))
         W1, Wh, Ww = (p.detach().reshape(p.shape[0], -1) for p in (w1, wh, ww))
         dpool = ops.coordatt_mlp_bwd(pool, n, h, w, c, ctx.mip, W1, b1.detach(), mean, invstd, gamma.detach(), beta.detach(), Wh, Ww, a_h, a_w,
-                                     da_h, da_w, targets)
-        if fresh64:
-            rounded, k, out = ops.f64_round(targets, shapes), 0, []
-            for i, r in enumerate(ret):
-                if i == 1:
-                    out.append(r)
-                    continue
-                out.append(rounded[k] if r is not None else None)
-                k += 1
-            ret = out
+                                     da_h, da_w, grads.bufs)
+        ret = grads.values()
         ops.pool_hw_bwd(dpool, n, h, w, c, into=dx)
-        for i, (p, r) in enumerate(zip(ctx.params, ret)):
-            if r is None and p.requires_grad and not (defer and i != 1):
-                ops.grad_done(p)
+        grads.finish()
         return (None, dx, *ret)
 
 
@@ -1010,16 +931,8 @@ def _rf_getw_bwd(ctx, sv, d_rfa, hk, wk):
 def _rf_gen_bn_coeffs(ctx, sv, sums, ch, count, transpose):
     """generate BatchNorm backward from the (striped) sums over its `ch` channels -> alpha, kappa, lambda of the passes that follow, and the
     return slots of its weight and bias.  transpose = (t, c): the sums are in [t][c] order (k = 3), the parameters in [c][t]"""
-    tgg, tgb = (ops.grad_target(q) for q in ctx.gen_bn_params)
-    bn_direct = all(q is not None and q.numel() == ch and q.is_contiguous() for q in (tgg, tgb))
-    dgg, dbg, alpha, kappa, lam = ops.bn_bwd_coeffs(sums, ch, count, sv.ag, sv.gmean_tc, sv.ginv_tc, True, dgamma=tgg if bn_direct else None,
-                                                    dbeta=tgb if bn_direct else None, transpose=transpose)
-    if bn_direct:
-        ops.grad_done(ctx.gen_bn_params[0])
-        ops.grad_done(ctx.gen_bn_params[1])
-    elif transpose is not None:
-        dgg, dbg = dgg.view(transpose).t(), dbg.view(transpose).t()          # views: _rf_grads makes the copies, after the route's last kernel
-    return alpha, kappa, lam, dgg, dbg
+    dgg, dbg, alpha, kappa, lam = _bn_bwd_coeffs(*ctx.gen_bn_params, sums, ch, count, sv.ag, sv.gmean_tc, sv.ginv_tc, True, transpose)
+    return alpha, kappa, lam, dgg, dbg          # (fresh k = 3 values are views: _rf_grads makes the copies, after the route's last kernel)
 
 
 def _rf_se_bwd(ctx, sv, d_ca):
@@ -1027,30 +940,26 @@ def _rf_se_bwd(ctx, sv, d_ca):
     return slots of the two linears.  d_ca: fp32 or float64 [n, c]"""
     n, c, h, w = ctx.geom[:4]
     se_wa, se_wb = ctx.se_params
-    ta, tb = ops.grad_target(se_wa), ops.grad_target(se_wb)
-    se_direct = ta is not None and tb is not None
-    dwa = ta if se_direct else torch.zeros(se_wa.shape, dtype=torch.float32, device=d_ca.device)
-    dwb = tb if se_direct else torch.zeros(se_wb.shape, dtype=torch.float32, device=d_ca.device)
-    dgap = ops.se_bwd(sv.se_part, n, h * w, c, se_wa.detach(), se_wb.detach(), se_wa.shape[0], sv.ca, d_ca, dwa, dwb)
-    if se_direct:
-        ops.grad_done(se_wa)
-        ops.grad_done(se_wb)
-        return dgap, None, None
-    return dgap, dwa, dwb
-
-
-def _rf_dbias(ctx, sv):
-    return None if ops.grad_target(ctx.conv_b_param) is not None else torch.zeros_like(sv.bias)      # BN removes the batch mean: d/dbias = 0
+    g = ops.ParamGrad(se_wa, se_wb, accept=ops.CONTIGUOUS)            # ly_se_bwd writes both: the sink takes both or neither
+    dgap = ops.se_bwd(sv.se_part, n, h * w, c, se_wa.detach(), se_wb.detach(), se_wa.shape[0], sv.ca, d_ca, *g.bufs)
+    return (dgap, *g.finish())
 
 
 def _rf_gen_w_fold(ctx, sv, dwg):
     """rows of partial sums of d(generate.0.weight) -> its return slot (a contiguous sink takes the fold itself)"""
-    tgw = ops.grad_target(ctx.gen_w_param)
-    if tgw is not None and tgw.is_contiguous() and tgw.numel() == dwg[0].numel():
-        ops.sum_rows(dwg, out=tgw.view(-1), accumulate=True)
-        ops.grad_done(ctx.gen_w_param)
-        return None
-    return ops.sum_rows(dwg).view(sv.gen_w.shape)
+    g = ops.ParamGrad(ctx.gen_w_param, accept=ops.CONTIGUOUS)
+    if g.direct:
+        ops.sum_rows(dwg, out=g.buf.view(-1), accumulate=True)
+        return g.finish()
+    return g.finish(ops.sum_rows(dwg).view(sv.gen_w.shape))
+
+
+def _rf_conv_w_grad(ctx, sv):
+    """where the gradient of conv.0.weight goes, as the rows [o][tap][c] every route's kernels write: the sink's storage when it is in that
+    order (a tap-major k = 3 target; at k = 1 the weight's own order), else fresh [o, kk*c] zeros returned in the weight's layout"""
+    c, k, o = ctx.geom[1], ctx.geom[4], ctx.geom[6]
+    return ops.ParamGrad(ctx.conv_w_param, accept=ops.TAP_ROWS, fresh=lambda: torch.zeros(o, k * k * c, dtype=torch.float32, device=sv.xr.device),
+                         view=lambda t: t.view(o, k * k, c).permute(0, 2, 1).reshape(sv.conv_w.shape))
 
 
 def _rf_grads(ctx, dx, dwa, dwb, dgw, dgg, dbg, dw18, dwc, dbias, dgo, dbo):
@@ -1063,7 +972,7 @@ def _rf_grads(ctx, dx, dwa, dwb, dgw, dgg, dbg, dw18, dwc, dbias, dgo, dbo):
 def _rfcbam_backward_streamed(ctx, sv, du, dgo, dbo):
     """RFCBAMConv backward on 9x-sized tensors in HBM (csrc/ly_rfcbam_bwd.hip), every k and width: generate, attention, ReLU, generate weight
     gradient and dx passes"""
-    xr, ca, gen_w, conv_w, ag, bg, rfa = sv.xr, sv.ca, sv.gen_w, sv.conv_w, sv.ag, sv.bg, sv.rfa
+    xr, ca, gen_w, ag, bg, rfa = sv.xr, sv.ca, sv.gen_w, sv.ag, sv.bg, sv.rfa
     n, c, h, w, k, s, o, ho, wo, ld = ctx.geom
     kk, mo = k * k, n * ho * wo
     dev, dt = xr.device, xr.dtype
@@ -1098,19 +1007,9 @@ def _rfcbam_backward_streamed(ctx, sv, du, dgo, dbo):
             L.check(L.lib().ly_rf_bwd_attn(n, h, w, c, k, s, p(ug), p(dcd), p(ag), p(bg), p(ca), p(rfa), p(cd), p(d_rfa), p(gmax), p(d_ca), code, st),
                     "ly_rf_bwd_attn")
     # 6. conv weight gradient
-    tgt = ops.grad_target(ctx.conv_w_param)            # k = 1: the weight's own layout is what ly_wgrad writes
-    if tgt is not None and kk == 1:
-        ops.wgrad(M=mo, H=ho, W=wo, N=o, du=du, lddu=o, x=cd, ldx=c, Hin=ho, Win=wo, Cin=c, dw=tgt, lddw=c)
-        ops.grad_done(ctx.conv_w_param)
-        dwc = None
-    elif _tap_major_rows(tgt) is not None:                  # k = 3 with a tap-major sink: [o][t][c] is the storage's own order
-        ops.wgrad(M=mo, H=ho, W=wo, N=o, du=du, lddu=o, x=cd, ldx=kk * c, Hin=ho, Win=wo, Cin=kk * c, dw=_tap_major_rows(tgt), lddw=kk * c)
-        ops.grad_done(ctx.conv_w_param)
-        dwc = None
-    else:
-        dwc = torch.zeros(o, kk * c, dtype=torch.float32, device=dev)      # handed to autograd (k = 1: as a view): not from the pool
-        ops.wgrad(M=mo, H=ho, W=wo, N=o, du=du, lddu=o, x=cd, ldx=kk * c, Hin=ho, Win=wo, Cin=kk * c, dw=dwc, lddw=kk * c)
-        dwc = dwc.view(o, kk, c).permute(0, 2, 1).reshape(conv_w.shape)
+    gwc = _rf_conv_w_grad(ctx, sv)
+    ops.wgrad(M=mo, H=ho, W=wo, N=o, du=du, lddu=o, x=cd, ldx=kk * c, Hin=ho, Win=wo, Cin=kk * c, dw=gwc.buf, lddw=kk * c)
+    dwc = gwc.finish()
     # 7. get_weight + sigmoid
     d_mm, dw18 = _rf_getw_bwd(ctx, sv, d_rfa, k * ho, k * wo)
     # 8. through max/mean, ca, rfa and ReLU; generate-BN sums
@@ -1140,13 +1039,13 @@ def _rfcbam_backward_streamed(ctx, sv, du, dgo, dbo):
         args = (n, h, w, c, k, s, p(dcd), p(wg), p(dx), c, p(dgap), 1.0 / (h * w), code)
         with ops._Timed(ops._label("ly_rf_bwd_dx_describe", *args), 0.0, es9 + xr.element_size() * n * h * w * c, valu_flops=2.0 * mo * kk * kk * c):
             L.check(L.lib().ly_rf_bwd_dx(*args, st), "ly_rf_bwd_dx")
-    dbias = _rf_dbias(ctx, sv)
+    dbias = ops.zero_bias_grad(sv.bias, ctx.conv_b_param)
     return _rf_grads(ctx, dx, dwa, dwb, _rf_gen_w_fold(ctx, sv, dwg), dgg, dbg, dw18, dwc, dbias, dgo, dbo)
 
 
 def _rfcbam_backward_rc(ctx, sv, du, dgo, dbo):
     """RFCBAMConv k=3 backward on csrc/ly_rf3c_bwd.hip: no 9x-sized tensor in HBM — three recompute passes + the conv weight gradient"""
-    xr, ca, conv_w, mm, rfa = sv.xr, sv.ca, sv.conv_w, sv.mm, sv.rfa
+    xr, ca, mm, rfa = sv.xr, sv.ca, sv.mm, sv.rfa
     n, c, h, w, k, s, o, ho, wo, ld = ctx.geom
     dev = xr.device
     L = _lib()
@@ -1173,14 +1072,12 @@ def _rfcbam_backward_rc(ctx, sv, du, dgo, dbo):
     # conv weight gradient (independent of the chain below)
     with ops._Timed("ly_rf3c_wgrad_kernel", 2.0 * mo * 9 * c * o, xb, valu_flops=2.0 * mo * c * 81):
         L.check(L.lib().ly_rf3c_wgrad(ctypes.byref(P), st), "ly_rf3c_wgrad")
-    trows = _tap_major_rows(ops.grad_target(ctx.conv_w_param))
-    if trows is not None:                                       # tap-major sink: the fold of the partials adds straight into the gradient storage
-        ops.sum_rows(dwc_part.view(ng, o, 9 * c), out=trows, accumulate=True)
-        ops.grad_done(ctx.conv_w_param)
-        dwc = None
+    gwc = _rf_conv_w_grad(ctx, sv)
+    if gwc.direct:                                              # tap-major sink: the fold of the partials adds straight into the gradient storage
+        ops.sum_rows(dwc_part.view(ng, o, 9 * c), out=gwc.buf, accumulate=True)
+        dwc = gwc.finish()
     else:
-        dwc = ops.sum_rows(dwc_part) if ng > 1 else dwc_part[0]
-        dwc = dwc.permute(0, 2, 1).reshape(conv_w.shape)
+        dwc = gwc.finish(ops.sum_rows(dwc_part) if ng > 1 else dwc_part[0])
     # get_weight + sigmoid
     d_rfa = ops.sum_rows(d_rfa_part).view_as(rfa) if nch > 1 else d_rfa_part[0].view_as(rfa)
     d_mm, dw18 = _rf_getw_bwd(ctx, sv, d_rfa, 3 * ho, 3 * wo)
@@ -1199,7 +1096,7 @@ def _rfcbam_backward_rc(ctx, sv, du, dgo, dbo):
     # pass C: regenerate (81 MAC) + generate weight gradient (81) + dx (81) per (output pixel, channel) on the VALU; dG = W^T du on the MFMAs
     with ops._Timed(f"ly_rf3c_bwd_kernel<2, {o // 32}>", 2.0 * mo * 9 * c * o, xb + xr.element_size() * n * h * w * c, valu_flops=2.0 * mo * c * 243):
         L.check(L.lib().ly_rf3c_bwd(ctypes.byref(P), 2, st), "ly_rf3c_bwd C")
-    dbias = _rf_dbias(ctx, sv)
+    dbias = ops.zero_bias_grad(sv.bias, ctx.conv_b_param)
     return _rf_grads(ctx, dx, dwa, dwb, _rf_gen_w_fold(ctx, sv, dwg), dgg, dbg, dw18, dwc, dbias, dgo, dbo)      # (dwg: one row per image)
 
 
@@ -1207,7 +1104,7 @@ def _rfcbam_backward_k1(ctx, sv, du, dgo, dbo):
     """RFCBAMConv kernel_size 1 backward on the fused recompute passes (csrc/ly_rf1_bwd.hip): G = relu(bn(gw*x)) is recomputed from x in
     every pass, nothing the size of the input is stored except cd (the conv weight gradient's operand) and dx.  du: gradient of the conv
     output (after the output BatchNorm / ReLU backward)."""
-    xr, ca, gen_w, conv_w, ag, bg, rfa = sv.xr, sv.ca, sv.gen_w, sv.conv_w, sv.ag, sv.bg, sv.rfa
+    xr, ca, gen_w, ag, bg, rfa = sv.xr, sv.ca, sv.gen_w, sv.ag, sv.bg, sv.rfa
     n, c, h, w, k, s, o, ho, wo, ld = ctx.geom
     dev, dt = xr.device, xr.dtype
     L = _lib()
@@ -1232,15 +1129,9 @@ def _rfcbam_backward_k1(ctx, sv, du, dgo, dbo):
     with ops._Timed(f"ly_rf1_bwd_kernel<{tn}, 0>", 6.0 * mo * c, 3.0 * es1):
         L.check(L.lib().ly_rf1_bwd(ctypes.byref(P), 0, st), "ly_rf1_bwd A")
     # conv weight gradient from cd
-    tgt = ops.grad_target(ctx.conv_w_param)
-    if tgt is not None:
-        ops.wgrad(M=mo, H=h, W=w, N=o, du=du, lddu=o, x=cd, ldx=c, Hin=h, Win=w, Cin=c, dw=tgt, lddw=c)
-        ops.grad_done(ctx.conv_w_param)
-        dwc = None
-    else:
-        dwc = torch.zeros(o, c, dtype=torch.float32, device=dev)
-        ops.wgrad(M=mo, H=h, W=w, N=o, du=du, lddu=o, x=cd, ldx=c, Hin=h, Win=w, Cin=c, dw=dwc, lddw=c)
-        dwc = dwc.view(conv_w.shape)
+    gwc = _rf_conv_w_grad(ctx, sv)
+    ops.wgrad(M=mo, H=h, W=w, N=o, du=du, lddu=o, x=cd, ldx=c, Hin=h, Win=w, Cin=c, dw=gwc.buf, lddw=c)
+    dwc = gwc.finish()
     # get_weight + sigmoid
     d_mm, dw18 = _rf_getw_bwd(ctx, sv, d_rfa, h, w)
     # BatchNorm sums of the generate BatchNorm (double accumulators)
@@ -1255,7 +1146,7 @@ def _rfcbam_backward_k1(ctx, sv, du, dgo, dbo):
     with ops._Timed(f"ly_rf1_bwd_kernel<{tn}, 2>", 10.0 * mo * c, 3.0 * es1):
         L.check(L.lib().ly_rf1_bwd(ctypes.byref(P), 2, st), "ly_rf1_bwd C")
     dgw = ggw.finish()
-    return _rf_grads(ctx, dx, dwa, dwb, dgw, dgg, dbg, dw18, dwc, _rf_dbias(ctx, sv), dgo, dbo)
+    return _rf_grads(ctx, dx, dwa, dwb, dgw, dgg, dbg, dw18, dwc, ops.zero_bias_grad(sv.bias, ctx.conv_b_param), dgo, dbo)
 
 
 RC_BWD_WIDTHS = (64, 128)           # output widths on the recompute passes (see RfcbamFn.backward); a module constant: tools / tests monkeypatch it

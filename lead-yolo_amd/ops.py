@@ -818,6 +818,110 @@ class SmallGrad:
         return None
 
 
+class _SmallGradGroup:
+    """SmallGrad.group(params, zero): the small gradients of ONE kernel with a single float64 flag (CoordAtt's MLP backward) take one route:
+      1. deferred float64 scratches (small_grad_scratch): inside a backward pass, every gradient bound for a contiguous sink target;
+      2. fresh float64 buffers rounded by ONE f64_round launch in values(): no sink target anywhere, DETERMINISTIC_SMALL_GRADS;
+      3. fp32 as they are: each one's sink target, or fresh zeros.
+    params[i], i in `zero`, has a zero gradient (zero_bias_grad) and no buffer.  A parameter that does not require grad gets a buffer (the
+    kernel writes all of `bufs`), but nothing is returned or announced for it."""
+
+    def __init__(self, params, zero=()):
+        self.params, self.zero, self.ret, self.bufs = params, zero, [], []
+        for i, p in enumerate(params):
+            if i in zero:
+                self.ret.append(zero_bias_grad(p, p) if p.requires_grad else None)
+                continue
+            t = grad_target(p)
+            self.bufs.append(t if t is not None else torch.zeros(p.shape, dtype=torch.float32, device=p.device))
+            self.ret.append(self.bufs[-1] if t is None and p.requires_grad else None)
+        live = [p for i, p in enumerate(params) if i not in zero]
+        self.deferred = small_grads_ok() and all(r is None for r in self.ret) and all(b.is_contiguous() for b in self.bufs)
+        self.fresh64 = not self.deferred and DETERMINISTIC_SMALL_GRADS and all(grad_target(p) is None for p in live)
+        if self.deferred:
+            self.bufs = [small_grad_scratch(b, p if p.requires_grad else None) for b, p in zip(self.bufs, live)]
+        elif self.fresh64:
+            self.shapes = [b.shape for b in self.bufs]
+            self.bufs = [zeros_f64(b.numel(), b.device) for b in self.bufs]
+
+    def values(self):              # once the kernel that fills `bufs` is in the stream -> the return values in the order of `params`
+        if self.fresh64:
+            rounded = iter(f64_round(self.bufs, self.shapes))
+            for i, r in enumerate(self.ret):
+                if i not in self.zero:
+                    v = next(rounded)
+                    self.ret[i] = v if r is not None else None
+        return self.ret
+
+    def finish(self):              # after the node's last launch, where it always announced: the listeners are told of what went to the sink
+        for i, (p, r) in enumerate(zip(self.params, self.ret)):
+            if r is None and p.requires_grad and (i in self.zero or not self.deferred):      # (deferred: announced by flush_small_grads)
+                grad_done(p)
+
+
+SmallGrad.group = _SmallGradGroup
+
+
+def zero_bias_grad(like, param=None):
+    """gradient of a convolution bias in front of a train-mode BatchNorm: BN removes the batch mean, d/dbias = 0.  Zeros of `like` for
+    autograd to accumulate — or, with `param`, None when a sink holds the bias's gradient storage (adding zero launches nothing)."""
+    return None if grad_target(param) is not None else torch.zeros_like(like)
+
+
+OWN, CONTIGUOUS, TAP_ROWS = "own", "contiguous", "tap_rows"          # the sink-target layouts a kernel can add into (ParamGrad)
+
+
+def tap_major(g):
+    """gradient tensor of a [co, ci, kh, kw] weight whose storage is [co][kh][kw][ci] (see optim.FusedSGD)"""
+    return g.dim() == 4 and not g.is_contiguous() and g.stride(1) == 1 and g.stride(3) == g.shape[1]
+
+
+def _sink_view(param, accept):
+    """the sink's tensor for `param` as a kernel that writes the layout `accept` adds into it, or None: no target, or not in that layout.
+    OWN: whatever the target's strides are (the kernel takes them: ly_wgrad's dw_ts / dw_cs).  CONTIGUOUS: the parameter's own order.
+    TAP_ROWS: [co, taps * ci] rows in [co][tap][ci] order — the storage behind a tap-major k x k target, a contiguous one-tap target."""
+    t = grad_target(param)
+    if t is None or accept == OWN:
+        return t
+    if accept == TAP_ROWS and t.dim() == 4 and t.shape[2] * t.shape[3] > 1:
+        rows = t.permute(0, 2, 3, 1)            # (not contiguous: a reshape would hand out a copy, and the gradient written into it be lost)
+        return rows.view(t.shape[0], -1) if tap_major(t) and rows.is_contiguous() else None
+    return t if t.is_contiguous() and t.numel() == param.numel() else None
+
+
+class ParamGrad:
+    """Where the full-size fp32 gradient of ONE parameter goes — or of several that one kernel writes together (gamma / beta through
+    ly_bn_bwd_coeffs, the SE linears through ly_se_bwd): the sink takes all or none.  `direct`: into the sink's storage, in the layout
+    `accept`.  `bufs` (`buf`: the first) is what the kernels ADD into: the sink's tensors, else zeros made on first use — by torch.zeros,
+    not from the step pool (they go to autograd), of the parameter's shape, or what the callable `fresh` returns (the caller's own
+    storage).  `targets`: the sink's tensors or Nones, for a wrapper that makes its own fresh ones.  finish() is called once the launches
+    that fill `bufs` are in the stream (or queued in _WgradQueue): direct -> the listeners are told, None; else what the autograd function
+    returns: `bufs` — or the `values` the consumer made instead — each through `view`.  One parameter: one value; several: a tuple."""
+
+    def __init__(self, *params, accept=OWN, fresh=None, view=None):
+        self.params, self._fresh, self._view = params, fresh, view
+        views = [_sink_view(p, accept) for p in params]
+        self.direct = all(v is not None for v in views)
+        self.targets = views if self.direct else [None] * len(params)
+        self._bufs = views if self.direct else None
+
+    @property
+    def bufs(self):
+        if self._bufs is None:
+            f = self._fresh() if self._fresh is not None else [torch.zeros(p.shape, dtype=torch.float32, device=p.device) for p in self.params]
+            self._bufs = [f] if torch.is_tensor(f) else list(f)
+        return self._bufs
+
+    buf = property(lambda self: self.bufs[0])
+
+    def finish(self, *values):
+        if self.direct:
+            for p in self.params:
+                grad_done(p)
+        out = [None if self.direct else v if self._view is None else self._view(v) for v in (values or self.bufs)]
+        return out[0] if len(out) == 1 else tuple(out)
+
+
 def mlpblock(x, y, n, h, w, c, wp, w1, w2, sc, sh, stats=None):
     m = n * h * w
     with _Timed(_label("ly_mlpblock_fwd_describe", n, h, w, c, capi.dtype_code(x), int(stats is not None)), 2.0 * m * (9 * (c // 4) ** 2 + 4 * c * c),
@@ -1056,11 +1160,15 @@ class GradSink:
     """Where the backward kernels put parameter gradients.  Default (no sink installed): fresh tensors handed to autograd, which
     accumulates them into `.grad` — one extra launch per parameter and step, plus the zero fill of every fresh tensor.  With a sink
     (optim.FusedSGD installs one: its persistent, step-zeroed gradient storage) ly_wgrad / ly_bn_bwd_coeffs ADD straight into
-    `param.grad` and the autograd function returns None for that parameter; `done(param)` then stands in for the post-accumulate
-    hook (ddp.GradReducer launches a bucket's all-reduce from it)."""
+    `param.grad` and the autograd function returns None for that parameter; `grad_done(param)` then stands in for the post-accumulate
+    hook (ddp.GradReducer launches a bucket's all-reduce from it).
+    The invariant whoever fills `targets` keeps (optim's fused optimisers, over their own storage or ddp.GradReducer's bucket views): a
+    target has its parameter's SHAPE, is fp32 and is contiguous — or, for a k x k convolution weight, tap-major (`tap_major`).  Which of
+    the two layouts a kernel can add into is a fact about the kernel: its caller names it (OWN / CONTIGUOUS / TAP_ROWS) to ParamGrad,
+    the one place that decides between the sink and a fresh tensor."""
 
     def __init__(self):
-        self.targets = {}          # id(param) -> gradient tensor (same shape as the parameter, fp32, contiguous)
+        self.targets = {}          # id(param) -> gradient tensor (see the invariant above)
         self.writes = 0            # bumped whenever a backward kernel is handed a target (or a captured backward is replayed): the
                                    # optimiser's zero_grad() compares it with the value at its last step() to know whether the storage is dirty
 

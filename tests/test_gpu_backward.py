@@ -138,11 +138,17 @@ def _with_sink_cases(cases, pick):
         [pytest.param(*case, True, id=i + "-sink") for case, i in zip(cases, ids) if pick(case)]
 
 
-@pytest.mark.parametrize("kind,ctor,shape,sink", _with_sink_cases(BWD_CASES, lambda case: case[0] == "RFCBAMConv"))
+# the smallest case of every other node family, repeated with the sink: fused MLPBlock backward, unfused, composed ConvBnAct nodes,
+# ConvBnActPair + CoordAttFn, PatchMerging, SPPF
+SINK_CASES = {("BasicStage", (24, 1)), ("BasicStage", (160, 1)), ("BasicStage", (48, 2)), ("C3_CA", (64, 64, 3, True)),
+              ("PatchMerging_FasterNet", (40, 80, 2, 2)), ("SPPF", (320, 320, 5))}
+
+
+@pytest.mark.parametrize("kind,ctor,shape,sink", _with_sink_cases(BWD_CASES, lambda case: case[0] == "RFCBAMConv" or case[:2] in SINK_CASES))
 def test_module_backward_shapes_vs_oracle(kind, ctor, shape, sink, monkeypatch):
     """real layer shapes and ragged sizes: every gradient elementwise against autograd through the oracle.  sink: the RFCBAMConv routes
-    (k = 1 recompute, streamed with ly_rf3s_bwd, ragged, streamed thread = channel passes, generic k = 1) once more with the parameter
-    gradients written straight into an optimiser's storage"""
+    (k = 1 recompute, streamed with ly_rf3s_bwd, ragged, streamed thread = channel passes, generic k = 1) and the smallest case of every
+    other node family once more with the parameter gradients written straight into an optimiser's storage"""
     torch.manual_seed(0)
     m = _ctor(kind)(*ctor)
     st = synth.synth_state(synth.shapes_of(m.state_dict()), 9100 + sum(shape) + len(kind))
