@@ -179,3 +179,31 @@ def test_fingerprint_moves_with_every_route():
     moved("optim.step")
     pack.touch()                                       # ly_bn_finalize's signal (running statistics written by a kernel)
     moved("pack.touch")
+
+
+def test_bn_train_args_refuses_and_touches_only_for_tracked_statistics():
+    """ops._bn_train_args, which gathers a train-mode BatchNorm's arguments for the finalize kernels (what any route that shares it must
+    keep): momentum=None with tracked statistics is refused (the kernels compute no cumulative average) before anything is announced;
+    without tracked statistics the running-stat pointers are null and no cache is invalidated; with them the epoch moves (the kernel
+    writes behind torch's version counters)"""
+    import pytest
+
+    from lead_yolo_amd import ops
+    bn = torch.nn.BatchNorm2d(4, momentum=None).train()
+    before = pack.versions()
+    with pytest.raises(NotImplementedError):
+        ops._bn_train_args(bn)
+    assert pack.versions() == before
+    with pytest.raises(NotImplementedError):
+        ops._bn_train_args(torch.nn.BatchNorm2d(4).train().half())
+    assert pack.versions() == before
+    for momentum in (None, 0.1):
+        free = torch.nn.BatchNorm2d(4, momentum=momentum, track_running_stats=False).train()
+        gamma, beta, eps, mom, running_mean, running_var, nbt = ops._bn_train_args(free)
+        assert running_mean.value is None and running_var.value is None and nbt.value is None
+        assert gamma.value == free.weight.data_ptr() and beta.value == free.bias.data_ptr() and eps == free.eps
+        assert pack.versions() == before
+    bn = torch.nn.BatchNorm2d(4, momentum=0.25).train()
+    gamma, beta, eps, mom, running_mean, running_var, nbt = ops._bn_train_args(bn)
+    assert (running_mean.value, running_var.value, nbt.value) == (bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr())
+    assert mom == 0.25 and pack.versions() != before
