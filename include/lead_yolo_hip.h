@@ -197,7 +197,7 @@ int ly_se_fwd(const void* x /*T*/, int ldx, int n_img, int HW, int C, const floa
  * k = 1: a1/b1 = folded per-channel scale/shift.  k = 3: wg = pack.rfcbam_gen_weights(..., 32, False):
  * [C32/32][4 waves][9 t][4 channel pairs][20]; TH x TW (<= 64) = output-pixel tile per block.
  * part != NULL: the SAME pass also leaves the partial sums of SE's global average pool (models/rfa.py:90), part[n][slice][C]
- * (k = 1: slices = pixel slices per image, free; k = 3: one row per output tile, slices = ceil(Ho/TH)*ceil(Wo/TW)) for
+ * (k = 1: slices = pixel slices per image, free; k = 3, stride 1 or 2 only: one row per output tile, slices = ceil(Ho/TH)*ceil(Wo/TW)) for
  * ly_rfcbam_mid / ly_se_mlp — x is then read once instead of twice before the contraction.                              */
 int ly_rfcbam_stats(const void* x /*T*/, int ldx, int n_img, int H, int W, int C, int k, int s, const float* wg,
                     const float* a1, const float* b1, int TH, int TW, float* mm, float* part, int slices, int dtype, void* stream);

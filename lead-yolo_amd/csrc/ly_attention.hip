@@ -616,6 +616,8 @@ static int rfcbam_stats_entry(const void* x, int ldx, int n_img, int H, int W, i
   const int Ho = (H + 2 - 3) / s + 1, Wo = (W + 2 - 3) / s + 1;
   const int nct = (Wo + TW - 1) / TW, nrt = (Ho + TH - 1) / TH;
   LY_CHECK(!part || slices == nct * nrt, "rfcbam_stats: k=3 fused SE pooling writes one partial row per tile: slices must be %d", nct * nrt);
+  // the pooling reads the inputs a tile OWNS, s*TH x s*TW of them, out of the staged tile of s*(TH-1)+3 x s*(TW-1)+3: held for s <= 2 only
+  LY_CHECK(!part || s <= 2, "rfcbam_stats: k=3 fused SE pooling is built for stride 1 and 2 (stride %d: take the partials with ly_colsum)", s);
   const int IH = s * (TH - 1) + 3, IW = s * (TW - 1) + 3;
   size_t lds = sizeof(float) * ((size_t)4 * LY_ST3_WF + (size_t)IH * IW * (LY_SCC + 1) + 4 * 18 * 64);
   LY_CHECK(IH * IW * (LY_SCC / 4) <= LY_ST3_NV * LY_THREADS, "rfcbam_stats: input tile %dx%d exceeds the staging capacity", IH, IW);
