@@ -564,6 +564,45 @@ int ly_letterbox_u8(const LyLetterboxImage* imgs, int n_img, int maxH, int maxW,
 int ly_scale_boxes(const float* dets, const int* counts, int bs, int max_det, const float* shapes, int round_boxes, float* out,
                    void* stream);
 
+/* ---- whole scenes on the device (csrc/ly_scene.hip; lead-yolo_amd/scene.py SceneDetector) ------------------------------------------------
+ * A SAR scene (10 000 .. 30 000 pixels a side) runs at native resolution as overlapping tiles; the tiles' detections are merged in scene
+ * pixels.  The reference has no such stage: these entries replace what its user writes on the host around detect.py.                      */
+/* n windows of T x T pixels out of one scene -> the model's uint8 input.  Replaces the host loop `im = scene[y0:y0 + T, x0:x0 + T]`,
+ * cv2.copyMakeBorder(114) to T x T and the transpose((2, 0, 1))[::-1] of utils/dataloaders.py LoadImages.__next__, per tile.
+ * scene: device, H rows of W pixels, C = 3 (HWC BGR) or 1 (one grey plane), row pitch in bytes `pitch` >= W * C (a scene may be a row /
+ * column view of a larger array; any alignment).  origins: device [n][2] int32 = (y0, x0), 0 <= y0 < H, 0 <= x0 < W (an origin outside
+ * the scene gives an all-114 tile).  dst: device [n][3][T][T] uint8, planes R, G, B; T a multiple of 16, dst 16-byte aligned.
+ * Contract, bit for bit:  dst[k][c][v][u] = scene[y0 + v][x0 + u][2 - c]  (C = 1: the grey value in all three planes), and 114 wherever
+ * y0 + v >= H or x0 + u >= W.  Every source offset is computed in 64 bits.                                                                */
+int ly_scene_tiles_u8(const unsigned char* scene, int H, int W, int C, long pitch, const int* origins, int n, int T, unsigned char* dst,
+                      void* stream);
+/* The tiles' detections as one candidate list in scene pixels.  Replaces the host loop `det[:, [0, 2]] += x0; det[:, [1, 3]] += y0`, the
+ * clip to the scene and np.concatenate over the tiles.  dets [n_tiles][max_det][6] / counts [n_tiles]: what nms_padded returns for the
+ * tiles (tiles of several batches concatenated); origins [n_tiles][2] = (y0, x0).  One thread per row; row t * max_det + r of the output:
+ *   r < counts[t]:  x1, x2 -> min(max(x + (float)x0, 0), W),  y1, y2 -> min(max(y + (float)y0, 0), H)  in fp32, in that order of
+ *                   operations; conf and cls copied;  score = conf
+ *   otherwise:      the box row all zeros, score = -1.
+ * boxes [n_tiles * max_det][6], score [n_tiles * max_det].                                                                                 */
+int ly_scene_collect(const float* dets, const int* counts, const int* origins, int n_tiles, int max_det, int H, int W, float* boxes,
+                     float* score, void* stream);
+/* Greedy suppression ACROSS tiles.  Replaces the numpy de-duplication of the shifted boxes.  boxes [N][6]: ly_scene_collect's rows (row /
+ * max_det_tile is the row's tile); order [N] int64 / sorted_score [N]: torch.sort(score, descending=True, stable=True).  The first
+ * min(number of scores >= 0, max_merge) candidates are walked in order; candidate j is kept unless an earlier KEPT candidate i
+ *   comes from another tile (i / max_det_tile != j / max_det_tile — a pair of one tile is nms_padded's, so a scene of one tile returns what
+ *   the per-tile NMS returned),  has the same class (cls_i == cls_j, compared: ly_nms_greedy's cls * 7680 offset is no separation where
+ *   real coordinates exceed 7680) or agnostic != 0,  and  m(i, j) > thres;
+ * the walk stops after max_det kept boxes.  keep [max_det]: the kept rows' indices into boxes, in kept order, the rest 0; count [1].
+ * The metric, in fp32, one operation per step, in this order (the file is built with -ffp-contract=off):
+ *   iw = max(min(x2_i, x2_j) - max(x1_i, x1_j), 0);  ih = max(min(y2_i, y2_j) - max(y1_i, y1_j), 0);  inter = iw * ih;
+ *   area = (x2 - x1) * (y2 - y1)  per box;
+ *   metric 0 (IoU):                                den = (area_i + area_j) - inter
+ *   metric 1 (intersection over the smaller box):  den = min(area_i, area_j)   — an object cut by a tile border lies inside its full box in
+ *                                                  the neighbour tile: IoU far below any usable threshold, this about 1
+ *   m = den == 0 ? 0 : inter / den.
+ * One block; max_merge <= 30000 (the alive set in LDS).  No atomic whose order can change the result: the same keep in every run.         */
+int ly_scene_nms(const float* boxes, const long* order, const float* sorted_score, int N, int max_det_tile, int metric, float thres,
+                 int agnostic, int max_det, int max_merge, int* keep, int* count, void* stream);
+
 /* ---- backward building blocks of the training step (train.py:324 `scaler.scale(loss).backward()`) -------------
  * Data gradients of 1x1 / 3x3 stride-1 convolutions reuse ly_gemm_fwd / ly_conv3x3_fwd with transposed weights.   */
 

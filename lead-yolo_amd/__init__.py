@@ -17,3 +17,4 @@ from .metrics import ConfusionMatrix, MatchAccumulator, Validator, ValResult, ap
 from .predict import Detector, LetterboxPlan, letterbox, letterbox_plan, load_image_size, scale_boxes  # noqa: F401,E402
 from .valrun import ValPlan, ValRun, ValSet, val_labels, val_plan, validate  # noqa: F401,E402
 from .anchors import AnchorCheck, anchor_metric, check_anchors, evolve, kmean_anchors, kmeans, label_wh, mutation_table  # noqa: F401,E402
+from .scene import SceneDetector, scene_collect, scene_merge, scene_plan, scene_tiles  # noqa: F401,E402
