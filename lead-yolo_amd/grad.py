@@ -21,7 +21,7 @@ import os
 
 import torch
 
-from . import ops, pack
+from . import ops, pack, rfcbam
 from .ops import ACT_NONE, ACT_RELU, ACT_SILU  # noqa: F401
 
 
@@ -838,48 +838,19 @@ class RfcbamFn(torch.autograd.Function):
         xr, ld = ops.rows(x)
         n, c, h, w = xr.shape
         k, s, o = mod.kernel_size, mod.stride, mod.o
-        ho, wo = (h + 2 * (k // 2) - k) // s + 1, (w + 2 * (k // 2) - k) // s + 1
+        ho, wo = ops.rf_out_hw(h, w, k, s)
         P = mod._packed_train(ops.planes_of(xr))
-        if se_wa.dtype != torch.float32:
+        if se_wa.dtype != torch.float32 or gen_w.dtype != torch.float32:
             raise NotImplementedError("RFCBAMConv training needs float32 parameters (train under autocast, fp32 master weights)")
-        from . import modules as _m
-        rc = k == 3 and ops.rf3c_ok(c, s) and _m.RF3C             # lane = channel kernels (csrc/ly_rf3c.hip): the pooling partials come out of the statistics pass
-        if not rc:
-            # SE (models/rfa.py:88-92): pooling partials + the two linears, two launches; the partials are kept for the backward
-            ca, se_part = ops.se_attention(xr, ld, n, h * w, c, se_wa.detach(), se_wb.detach(), se_wa.shape[0], want_part=True)
         bias = conv_b.detach().float().contiguous()
-        if gen_w.dtype != torch.float32:
-            raise NotImplementedError("RFCBAMConv training needs float32 parameters (train under autocast, fp32 master weights)")
-        G = ops.rfcbam_gen_prepare(xr, ld, n, h, w, c, k, s, gen_w, mod.generate[1])          # generate BatchNorm: moments + ONE launch
-        ctx.rc = None
-        # every branch: ca, rfa, mm, se_part and its contraction (called below: an identity scale is made after the accumulators, as ever)
-        if k == 1:
-            a1, gb = G["a1"], G["gb"]
-            mm = ops.rfcbam_stats(xr, ld, n, h, w, c, 1, 1, a1=a1, b1=gb)
-            rfa = ops.rfa_map(mm, P["w18"])
-            kw = dict(M=n * h * w, H=h, W=w, K=c, N=o, a0=xr, lda0=ld, k0=c, wp=P["wp"], ldo=o, pro=ops.PRO_AFFINE_RELU_CA,
-                      p_scale=a1, p_shift=gb, p_ca=ca, rowscale=rfa)
-            contract = lambda **io: ops.gemm(e_scale=None, **kw, **io)
-        elif rc:
-            # three launches, x read twice: statistics + SE pooling partials | SE linears + get_weight conv | regenerate + contraction.  The RAW
-            # generate image (u = w.x, v = a*u + b) is what the backward re-evaluates bit for bit
-            th, tw = ops.pick_tile_c(ho, wo, s)
-            mm, se_part = ops.rf3c_stats(xr, ld, n, h, w, c, s, G["wq_c"], th, tw, raw=True)
-            ca, rfa = ops.rfcbam_mid(se_part, h * w, se_wa.detach(), se_wb.detach(), se_wa.shape[0], mm, P["w18"])
-            kw = dict(n=n, h=h, w=w, c=c, ho=ho, wo=wo, N=o, s=s, th=th, tw=tw, x=xr, ldx=ld, wq=G["wq_c"], ca=ca, rfa=rfa, wp=P["wp_c"], ldo=o, raw=True)
-            contract = lambda **io: ops.rf3c_fwd(e_scale=ops.ones_f32(bias.numel(), bias.device), **kw, **io)
-            ctx.rc = dict(th=th, tw=tw, wq=G["wq_c"])
-        else:
-            th, tw = ops.pick_tile(ho, wo)
-            mm = ops.rfcbam_stats(xr, ld, n, h, w, c, 3, s, wg=G["wq_stats"], th=th, tw=tw)
-            rfa = ops.rfa_map(mm, P["w18"])
-            kw = dict(n=n, h=h, w=w, c=c, ho=ho, wo=wo, N=o, s=s, th=th, tw=tw, x=xr, ldx=ld, wg=G["wq_main"], ca=ca, rfa=rfa, wp=P["wp"], ldo=o)
-            contract = lambda **io: ops.rfcbam3(e_scale=torch.ones_like(bias), **kw, **io)
-        # ONE contraction: statistics and the pre-BN value u (bias included) in the same launch; y = relu(es*u + t) is an elementwise
-        # pass and u is kept for the backward (was: statistics pass + main pass + a recompute in backward)
-        stats = ops.new_stats(o, xr.device)
-        u = ops.empty_nhwc(n, o, ho, wo, xr)
-        contract(out=u, e_shift=bias, stats=stats)
+        # the inference sequence (rfcbam.forward) with batch statistics.  generate BatchNorm: moments + ONE launch, behind SE's (pooling partials
+        # + the two linears, kept for the backward) on the routes whose statistics pass leaves no partials.  ONE contraction: statistics and the
+        # pre-BN value u (bias included) in the same launch; y = relu(es*u + t) is an elementwise pass and u is kept for the backward
+        u, kept = rfcbam.forward(rfcbam.select(True, xr.dtype, k, s, c, o, n, ho, wo), xr, ld, k, s, o, se=(se_wa.detach(), se_wb.detach(), se_wa.shape[0]),
+                                 w18=P["w18"], gen=lambda: ops.rfcbam_gen_prepare(xr, ld, n, h, w, c, k, s, gen_w, mod.generate[1]), packed=P, raw=True,
+                                 se_first=True, e_scale=None, e_shift=bias, want_stats=True)
+        ca, rfa, mm, se_part, ctx.rc, G, stats = kept
+        ctx.gen_wq = G["wq_c"]                  # the raw lane = channel generate image (None where C % 32 != 0): the recompute backward reads it again
         es, t, omean, oinv = ops.bn_finalize(mod.conv[1], stats, o, n * ho * wo, want_stats=True)
         out = torch.empty_like(u)
         ops.bnact_fwd(u, o, n * ho * wo, o, es, t, ACT_RELU, out, o)
@@ -908,7 +879,7 @@ class RfcbamFn(torch.autograd.Function):
                                            beta=ctx.out_bn_params[1])       # (straight into the sink when one holds them: returns None, None)
             # (o = 256 — layer 20 — measured SLOWER on the recompute passes than on the streamed 9x tensors: 1.08 vs 0.73 ms of kernels at bs = 64;
             # layer 17, o = 128: 0.95 vs 1.47 ms.  The wider layer stays on the first-generation backward.)
-            if ctx.rc is not None and dt == torch.bfloat16 and s == 2 and o in RC_BWD_WIDTHS:
+            if ctx.rc.name == "rf3c" and dt == torch.bfloat16 and s == 2 and o in RC_BWD_WIDTHS:
                 return _rfcbam_backward_rc(ctx, sv, du, dgo, dbo)
             vw = ops.vw_of(xr)
             if k == 1 and c % vw == 0 and c // vw <= 64 and ld % vw == 0:
@@ -1052,7 +1023,7 @@ def _rfcbam_backward_rc(ctx, sv, du, dgo, dbo):
     st = L.stream_ptr()
     p = L.ptr
     mo, nch = n * ho * wo, c // 32
-    th, tw, wq = ctx.rc["th"], ctx.rc["tw"], ctx.rc["wq"]
+    th, tw, wq = ctx.rc.th, ctx.rc.tw, ctx.gen_wq
     wct = pack.packed(pack.Src(ctx.conv_w_param, 9 * c, nrb=c, sra=1, srb=9, nc=o, sc=c * 9), o, 1)
     npos = n * 9 * ho * wo
     d_rfa_part = torch.empty((nch, npos), dtype=torch.float32, device=dev)

@@ -21,7 +21,7 @@ the eval path.
 import torch
 import torch.nn as nn
 
-from . import ops, pack
+from . import ops, pack, rfcbam
 from .ops import ACT_NONE, ACT_RELU, ACT_SILU, Lazy
 
 BN_EPS = 1e-3
@@ -497,12 +497,13 @@ class RFCBAMConv(_Holder):
             # conv.0.weight [o, c, 3, 3] read as [o][c/16 chunks][10 tap slots (9 real)][16 channels]: k = chunk*160 + t*16 + ch
             wsrc = pack.Src(cw.weight, o, srb=c * 9, nb=10, vb=9, nc=16, sa=144, sb=1, sc=9)
             d = dict(wq_stats=wq_stats, wq_main=wq_main, w18=w18, wp=pack.packed(wsrc, (c // 16) * 160, planes), es=es, eb=eb)
-            if ops.rf3c_ok(c, self.stride):
+            could = rfcbam.select(False, torch.bfloat16 if planes == 1 else torch.float32, k, self.stride, c, o).could
+            if "rf3c" in could:
                 d["wq_c"] = pack.rfcbam_gen_weights_c(gw, gs, gb)
                 d["wp_c"] = self._wp_c(planes)
-            if planes == 1 and RF3M and ops.rf3m_ok(torch.bfloat16, c, o, self.stride):     # (stride 1 / 2 only: other strides keep the lane = pixel kernels)
+            if "rf3m" in could:
                 d["wm_stats"] = pack.rf3m_stream(gw, gs, gb, pool_stride=self.stride)          # csrc/ly_rf3m.hip: generate on the matrix cores
-                d["wm"] = pack.rf3m_stream(gw, gs, gb, cw.weight, 4 if o % 128 == 0 else 2)
+                d["wm"] = pack.rf3m_stream(gw, gs, gb, cw.weight, ops.rf3m_mt(o))
             return d
         return self._prep.get(key, build, planes)
 
@@ -523,7 +524,7 @@ class RFCBAMConv(_Holder):
             w18 = self.get_weight[0].weight.detach().float().reshape(18).contiguous()
             if k == 1:
                 return dict(w18=w18, wp=pack.packed(pack.src_matrix(cw.weight, o, c), c, planes))
-            if ops.rf3c_ok(c, self.stride) and RF3C:
+            if "rf3c" in rfcbam.select(True, torch.bfloat16 if planes == 1 else torch.float32, k,self.stride, c, o).could:
                 return dict(w18=w18, wp_c=self._wp_c(planes))
             wsrc = pack.Src(cw.weight, o, srb=c * 9, nb=10, vb=9, nc=16, sa=144, sb=1, sc=9)
             return dict(w18=w18, wp=pack.packed(wsrc, (c // 16) * 160, planes))
@@ -536,7 +537,7 @@ class RFCBAMConv(_Holder):
         if isinstance(x, Lazy):
             x = x.materialize()
         k_, s_ = self.kernel_size, self.stride
-        pr = _probe(x, (x.shape[0], self.o, (x.shape[2] + 2 * (k_ // 2) - k_) // s_ + 1, (x.shape[3] + 2 * (k_ // 2) - k_) // s_ + 1))
+        pr = _probe(x, (x.shape[0], self.o, *ops.rf_out_hw(x.shape[2], x.shape[3], k_, s_)))
         if pr is not None:
             return pr
         if self.training:
@@ -544,59 +545,14 @@ class RFCBAMConv(_Holder):
             return grad.rfcbam_train(self, x)
         xr, ld = ops.rows(x)
         n, c, h, w = xr.shape
-        k, s = self.kernel_size, self.stride
         P = self._packed(ops.planes_of(xr))
-        wa, wb = self.se.fc[0].weight.detach().float().contiguous(), self.se.fc[2].weight.detach().float().contiguous()
-        # k = 1, three launches: (1) ONE pass over x leaves the [max, mean] statistics map AND the partial sums of SE's global average
-        # pool, (2) SE's linears and get_weight's 3x3 conv on the small maps, (3) the contraction.  k = 3, four: the pooling partials
-        # are their own pass.  (The reference reads x for the pool, again for `generate`, and walks the 9x tensor ~13 times.)
-        if k == 1:
-            a1, b1, es, eb = P["a1"], P["b1"], P["es"], P["eb"]
-            mm, part = ops.rfcbam_stats(xr, ld, n, h, w, c, 1, 1, a1=a1, b1=b1, gap=True)
-            ca, rfa = ops.rfcbam_mid(part, h * w, wa, wb, self.se.ratio, mm, P["w18"])
-            out = ops.empty_nhwc(n, self.o, h, w, xr)
-            ops.gemm(M=n * h * w, H=h, W=w, K=c, N=self.o, a0=xr, lda0=ld, k0=c, wp=P["wp"], out=out, ldo=self.o, pro=ops.PRO_AFFINE_RELU_CA,
-                     p_scale=a1, p_shift=b1, p_ca=ca, rowscale=rfa, e_scale=es, e_shift=eb, act=ACT_RELU)
-            return out
-        ho, wo = (h + 2 - 3) // s + 1, (w + 2 - 3) // s + 1
-        if RF3M and ops.rf3m_ok(xr, c, self.o, s, n, ho, wo):
-            return self._forward3_m(xr, ld, n, c, h, w, ho, wo, s, P, wa, wb)
-        # (inference in fp32 storage with more than 128 output channels: the lane = pixel kernels measure faster — layer 20 at bs=64: 215 vs 289 us —
-        # the two-plane operand tile of the lane = channel kernel leaves one block per CU there)
-        if ops.rf3c_ok(c, s) and RF3C and not (xr.dtype == torch.float32 and self.o > 128):
-            return self._forward3_c(xr, ld, n, c, h, w, ho, wo, s, P, wa, wb)
-        th, tw = ops.pick_tile(ho, wo)
-        part = ops.colsum(xr, ld, n, h * w, c)                                                 # k = 3: pooling partials as their own pass
-        mm = ops.rfcbam_stats(xr, ld, n, h, w, c, 3, s, wg=P["wq_stats"], th=th, tw=tw)
-        ca, rfa = ops.rfcbam_mid(part, h * w, wa, wb, self.se.ratio, mm, P["w18"])
-        out = ops.empty_nhwc(n, self.o, ho, wo, xr)
-        ops.rfcbam3(n=n, h=h, w=w, c=c, ho=ho, wo=wo, N=self.o, s=s, th=th, tw=tw, x=xr, ldx=ld, wg=P["wq_main"], ca=ca, rfa=rfa, wp=P["wp"],
-                    e_scale=P["es"], e_shift=P["eb"], out=out, ldo=self.o)
-        return out
-
-
-    def _forward3_c(self, xr, ld, n, c, h, w, ho, wo, s, P, wa, wb):
-        """k = 3, inference, on the lane = channel kernels (csrc/ly_rf3c.hip), three launches, x read twice: (1) [max, mean] map + SE pooling partials,
-        (2) SE linears + get_weight's conv on the small maps, (3) regenerate + contraction."""
-        th, tw = ops.pick_tile_c(ho, wo, s)
-        mm, part = ops.rf3c_stats(xr, ld, n, h, w, c, s, P["wq_c"], th, tw)
-        ca, rfa = ops.rfcbam_mid(part, h * w, wa, wb, self.se.ratio, mm, P["w18"])
-        out = ops.empty_nhwc(n, self.o, ho, wo, xr)
-        ops.rf3c_fwd(n=n, h=h, w=w, c=c, ho=ho, wo=wo, N=self.o, s=s, th=th, tw=tw, x=xr, ldx=ld, wq=P["wq_c"], ca=ca, rfa=rfa, wp=P["wp_c"],
-                     e_scale=P["es"], e_shift=P["eb"], out=out, ldo=self.o)
-        return out
-
-
-    def _forward3_m(self, xr, ld, n, c, h, w, ho, wo, s, P, wa, wb):
-        """k = 3, bf16, inference: `generate` as block-diagonal MFMA products whose accumulators feed the main contraction in registers
-        (csrc/ly_rf3m.hip) — (1) [max, mean] map + SE pooling partials, (2) SE linears + get_weight's conv, (3) generate + contraction"""
-        th, tw = ops.pick_tile_m(ho, wo, s)
-        mm, part = ops.rf3m_stats(xr, ld, n, h, w, c, s, P["wm_stats"], th, tw)
-        ca, rfa = ops.rfcbam_mid(part, h * w, wa, wb, self.se.ratio, mm, P["w18"])
-        out = ops.empty_nhwc(n, self.o, ho, wo, xr)
-        ops.rf3m_fwd(n=n, h=h, w=w, c=c, ho=ho, wo=wo, N=self.o, s=s, th=th, tw=tw, x=xr, ldx=ld, ca=ca, rfa=rfa, wp=P["wm"], e_scale=P["es"],
-                     e_shift=P["eb"], out=out, ldo=self.o)
-        return out
+        se = (self.se.fc[0].weight.detach().float().contiguous(), self.se.fc[2].weight.detach().float().contiguous(), self.se.ratio)
+        # k = 1 and the fused k = 3 routes, three launches: (1) ONE pass over x leaves the [max, mean] statistics map AND the partial sums of
+        # SE's global average pool, (2) SE's linears and get_weight's 3x3 conv on the small maps, (3) the contraction.  Lane = pixel k = 3,
+        # four: the pooling partials are their own pass.  (The reference reads x for the pool, again for `generate`, and walks the 9x tensor ~13 times.)
+        route = rfcbam.select(False, xr.dtype, k_, s_, c, self.o, n, *ops.rf_out_hw(h, w, k_, s_))
+        return rfcbam.forward(route, xr, ld, k_, s_, self.o, se=se, w18=P["w18"], gen=lambda: P, packed=P, raw=False, se_first=False,
+                              e_scale=P["es"], e_shift=P["eb"], want_stats=False)[0]
 
 
 RF3M = True        # tools / tests: False keeps the lane = channel kernels for the bf16 inference forward of k = 3

@@ -394,9 +394,19 @@ def pick_tile(ho, wo):
     return best[1], best[2]
 
 
+def rf_out_hw(h, w, k, s):
+    """output map of RFCBAMConv's `generate` (kernel k, padding k // 2, stride s) over an h x w input"""
+    return (h + 2 * (k // 2) - k) // s + 1, (w + 2 * (k // 2) - k) // s + 1
+
+
 def rf3c_ok(c, s):
     """the lane = channel RFCBAMConv k=3 kernels (csrc/ly_rf3c.hip) cover C % 32 == 0 at stride 1 / 2"""
     return c % 32 == 0 and s in (1, 2)
+
+
+def rf3m_mt(o):
+    """32-channel output tiles per block of ly_rf3m_fwd, and of pack.rf3m_stream's weight stream: 4 (128 channels) or 2 (64)"""
+    return 4 if o % 128 == 0 else 2
 
 
 RF3M_MIN_UNITS = 1500      # wave tiles x output-channel blocks below which the lane = channel kernels are faster (measured, MI355X, module time in us,
@@ -413,10 +423,13 @@ def rf3m_ok(x, c, o, s, n=None, ho=None, wo=None):
     is given, enough wave tiles to fill the chip (RF3M_MIN_UNITS)"""
     if not ((x if isinstance(x, torch.dtype) else x.dtype) == torch.bfloat16 and c % 32 == 0 and o % 64 == 0 and s in (1, 2)):
         return False
-    if n is None:
-        return True
+    return n is None or rf3m_units(n, ho, wo, o, s) >= RF3M_MIN_UNITS
+
+
+def rf3m_units(n, ho, wo, o, s):
+    """wave tiles x output-channel blocks of ly_rf3m_fwd over the whole batch (all CONCURRENT_PARTS sub-batches)"""
     th, tw = pick_tile_m(ho, wo, s)
-    return n * CONCURRENT_PARTS * -(-ho // th) * -(-wo // tw) * (o // (128 if o % 128 == 0 else 64)) >= RF3M_MIN_UNITS
+    return n * CONCURRENT_PARTS * -(-ho // th) * -(-wo // tw) * (o // (32 * rf3m_mt(o)))
 
 
 def pick_tile_m(ho, wo, s):
@@ -433,12 +446,18 @@ def pick_tile_m(ho, wo, s):
     return best[1], best[2]
 
 
+def _rf3_stats_out(x, n, h, w, c, s, th, tw, gap):
+    """what a fused k = 3 statistics pass (rf3c_stats, rf3m_stats) writes: (ho, wo, tiles, mm [n, 3ho, 3wo, 2], part [n, tiles, c] or None)"""
+    ho, wo = rf_out_hw(h, w, 3, s)
+    tiles = -(-ho // th) * -(-wo // tw)
+    mm = torch.empty((n, 3 * ho, 3 * wo, 2), dtype=torch.float32, device=x.device)
+    part = torch.empty((n, tiles, c), dtype=torch.float32, device=x.device) if gap else None
+    return ho, wo, tiles, mm, part
+
+
 def rf3m_stats(x, ldx, n, h, w, c, s, wst, th, tw, gap=True):
     """ONE pass over x (csrc/ly_rf3m.hip): (mm [n, 3ho, 3wo, 2], part [n, tiles, c])"""
-    ho, wo = (h + 2 - 3) // s + 1, (w + 2 - 3) // s + 1
-    mm = torch.empty((n, 3 * ho, 3 * wo, 2), dtype=torch.float32, device=x.device)
-    tiles = -(-ho // th) * -(-wo // tw)
-    part = torch.empty((n, tiles, c), dtype=torch.float32, device=x.device) if gap else None
+    ho, wo, tiles, mm, part = _rf3_stats_out(x, n, h, w, c, s, th, tw, gap)
     # generate on the MFMAs: 3 + 3 products of 32 x 32 x 16 per 4-channel group and 32 pixels (3/4 of them multiply structural zeros)
     with _Timed("ly_rf3m_stats_kernel", 2.0 * n * ho * wo * (c // 4) * 6 * 32 * 16, x.element_size() * n * h * w * c + 4.0 * 18 * n * ho * wo):
         capi.check(capi.lib().ly_rf3m_stats(_p(x), ldx, n, h, w, c, s, _p(wst), th, tw, _p(mm), _p(part), tiles, capi.stream_ptr()), "ly_rf3m_stats")
@@ -449,8 +468,7 @@ def rf3m_fwd(*, n, h, w, c, ho, wo, N, s, th, tw, x, ldx, ca, rfa, wp, e_scale, 
     P = capi.LyRfcbam3Params(n, h, w, c, ho, wo, N, s, th, tw, _p(x), ldx, None, _p(ca), _p(rfa), _p(wp), _p(e_scale),
                              _p(e_shift), _p(out), ldo, None, 0, capi.dtype_code(x))
     mo = n * ho * wo
-    mt = 4 if N % 128 == 0 else 2                          # (32-channel tiles per block of pack.rf3m_stream's weight stream: the flop count's)
-    with _Timed(_label("ly_rf3m_fwd_describe", ctypes.byref(P)), 2.0 * mo * 9 * c * N + 2.0 * mo * (N // (32 * mt)) * (c // 4) * 6 * 32 * 16,
+    with _Timed(_label("ly_rf3m_fwd_describe", ctypes.byref(P)), 2.0 * mo * 9 * c * N + 2.0 * mo * (N // (32 * rf3m_mt(N))) * (c // 4) * 6 * 32 * 16,
                 x.element_size() * (n * h * w * c + mo * N) + 2.0 * 9 * c * N):
         capi.check(capi.lib().ly_rf3m_fwd(ctypes.byref(P), capi.stream_ptr()), "ly_rf3m_fwd")
 
@@ -492,10 +510,7 @@ def pick_tile_bwd_dx(ho, wo, o):
 
 def rf3c_stats(x, ldx, n, h, w, c, s, wq, th, tw, gap=True, raw=False):
     """ONE pass over x: (mm [n, 3ho, 3wo, 2], part [n, tiles, c]) — the [max, mean] map of relu(bn(generate(x))) and SE's pooling partials"""
-    ho, wo = (h + 2 - 3) // s + 1, (w + 2 - 3) // s + 1
-    mm = torch.empty((n, 3 * ho, 3 * wo, 2), dtype=torch.float32, device=x.device)
-    tiles = -(-ho // th) * -(-wo // tw)
-    part = torch.empty((n, tiles, c), dtype=torch.float32, device=x.device) if gap else None
+    ho, wo, tiles, mm, part = _rf3_stats_out(x, n, h, w, c, s, th, tw, gap)
     with _Timed(f"ly_rf3c_stats_kernel<{_tname(x)}, {s}, {'true' if raw else 'false'}>", 0.0, x.element_size() * n * h * w * c + 4.0 * 18 * n * ho * wo, valu_flops=2.0 * n * ho * wo * c * 81):
         capi.check(capi.lib().ly_rf3c_stats(_p(x), ldx, n, h, w, c, s, _p(wq), int(raw), th, tw, _p(mm), _p(part), tiles, capi.dtype_code(x),
                                             capi.stream_ptr()), "ly_rf3c_stats")
@@ -517,7 +532,7 @@ PRE1_PIXELS = 64           # pixels per block of the k = 1 statistics + pooling 
 
 def rfcbam_stats(x, ldx, n, h, w, c, k, s, wg=None, a1=None, b1=None, th=1, tw=64, gap=False):
     """[max, mean] map of relu(bn(generate(x))); gap=True: the same pass also leaves the SE pooling partials -> (mm, part)"""
-    ho, wo = ((h + 2 * (k // 2) - k) // s + 1, (w + 2 * (k // 2) - k) // s + 1)
+    ho, wo = rf_out_hw(h, w, k, s)
     mm = torch.empty((n, k * ho, k * wo, 2), dtype=torch.float32, device=x.device)
     part, slices = None, 0
     if gap:
@@ -1234,7 +1249,7 @@ def rfcbam_gen_prepare(x, ldx, n, h, w, c, k, s, gen_w, bn):
         args = (_p(x), ldx, n, h, w, c, s, _p(mom), capi.dtype_code(x))
         with _Timed(_label("ly_rfcbam_tap_moments_describe", *args), 108.0 * n * h * w * c / (s * s), x.element_size() * n * h * w * c):
             capi.check(capi.lib().ly_rfcbam_tap_moments(*args, capi.stream_ptr()), "ly_rfcbam_tap_moments")
-        ho, wo = (h + 2 - 3) // s + 1, (w + 2 - 3) // s + 1
+        ho, wo = rf_out_hw(h, w, 3, s)
         count = n * ho * wo
     else:
         mom = chan_moments(x, ldx, n * h * w, c, striped=True)
