@@ -6,6 +6,12 @@
 // operand is read straight from the feature map (lane (pixel, g) loads the 8 channels 32 s + 8 g .. of its pixel per k-step: 64 contiguous bytes
 // per pixel over the four g), the two weight tiles (32 rows, natural k order: pack.frag_pack_nat) sit in LDS, and sigmoid / grid / anchor
 // arithmetic runs on the fp32 accumulators — the raw map is no longer rounded to bf16 on its way to p.
+//
+//   ly_detect_level, ly_detect_level_aug the one-launch level above, plain and with the test-time augmentation's _descale_pred
+//   ly_detect_level_ok                   whether (K, na, no, dtype) is built
+// Beside it, the pieces of the generic route and of the training step:
+//   ly_detect_tail, ly_detect_tail_aug   raw map + decode from the head GEMM's output y[n, h, w, na*no]          (models/yolo.py:95-120)
+//   ly_detect_head_bwd                   adjoint of the raw-map permute: dp -> the head's du rows and dbias        (models/yolo.py:88)
 #include "ly_common.hpp"
 #include "ly_tile.hpp"
 
@@ -199,4 +205,161 @@ extern "C" int ly_detect_level_aug(const void* x, int ldx, int n_img, int H, int
 extern "C" int ly_detect_level_ok(int K, int na, int no, int dtype) {
   const int S = K / 32;
   return (K % 32 == 0) && na * no <= 32 && (S == 2 || S == 4 || S == 8 || (S == 16 && dtype == LY_BF16));
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Detect tail (reference models/yolo.py:95-120): from the head GEMM output y[n, h, w, na*no] (row stride
+// ldy) write the raw map p[n, a, h, w, o] and, in eval mode, the decoded rows z[n, zoff + (a*H + h)*W + w, o]:
+//   xy = (2*sig - 0.5 + grid) * stride,  wh = (2*sig)^2 * anchor*stride,  rest = sig.
+// ---------------------------------------------------------------------------------------------------
+// AUG: the _descale_pred step of test-time augmentation on the decoded rows (see ly_detect_level_kernel above); p may be NULL there.
+template <typename T, bool AUG>
+__device__ __forceinline__ void ly_detect_tail_body(const T* __restrict__ y, int ldy, long total, int H, int W, int na, int no,
+                                                    const float* __restrict__ anchors /* [na,2] grid units */, float stride,
+                                                    float* __restrict__ p, float* __restrict__ z, long zrows, long zoff, float dscale, int dflip,
+                                                    float img_w) {
+  const long i = (long)blockIdx.x * LY_THREADS + threadIdx.x;      // over n*na*H*W*no, output order
+  if (i >= total) return;
+  const int o = (int)(i % no);
+  long t = i / no;
+  const int w = (int)(t % W); t /= W;
+  const int h = (int)(t % H); t /= H;
+  const int a = (int)(t % na);
+  const long n = t / na;
+  const float v = ly_ld1<T>(y + ((n * H + h) * W + w) * ldy + a * no + o);
+  if constexpr (AUG) {
+    if (p) p[i] = v;
+  } else {
+    p[i] = v;
+  }
+  if (z) {
+    const float s = ly_sigmoid(v);
+    float r = s;
+    if (o == 0) r = (s * 2.f + ((float)w - 0.5f)) * stride;
+    else if (o == 1) r = (s * 2.f + ((float)h - 0.5f)) * stride;
+    else if (o == 2 || o == 3) { const float q = s * 2.f; r = q * q * (anchors[a * 2 + (o - 2)] * stride); }
+    if constexpr (AUG) {
+      if (o < 4) r = r / dscale;
+      if (o == 0 && dflip) r = img_w - r;
+    }
+    z[(n * zrows + zoff + ((long)a * H + h) * W + w) * no + o] = r;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(LY_THREADS) void ly_detect_tail_kernel(const T* __restrict__ y, int ldy, long total, int H, int W, int na, int no,
+                                                                    const float* __restrict__ anchors /* [na,2] grid units */, float stride,
+                                                                    float* __restrict__ p, float* __restrict__ z, long zrows, long zoff) {
+  ly_detect_tail_body<T, false>(y, ldy, total, H, W, na, no, anchors, stride, p, z, zrows, zoff, 1.f, 0, 0.f);
+}
+
+template <typename T>
+__global__ __launch_bounds__(LY_THREADS) void ly_detect_tail_aug_kernel(const T* __restrict__ y, int ldy, long total, int H, int W, int na, int no,
+                                                                        const float* __restrict__ anchors, float stride, float* __restrict__ p,
+                                                                        float* __restrict__ z, long zrows, long zoff, float dscale, int dflip, float img_w) {
+  ly_detect_tail_body<T, true>(y, ldy, total, H, W, na, no, anchors, stride, p, z, zrows, zoff, dscale, dflip, img_w);
+}
+
+extern "C" int ly_detect_tail(const void* y, int ldy, int n_img, int H, int W, int na, int no, const float* anchors, float stride,
+                              float* p, float* z, long zrows, long zoff, int dtype, void* stream) {
+  LY_CHECK_DTYPE(dtype, "detect_tail");
+  LY_CHECK(y && p && anchors, "detect_tail: null pointer");
+  const long total = (long)n_img * na * H * W * no;
+  LY_WITH_T(dtype, hipLaunchKernelGGL(ly_detect_tail_kernel<T>, dim3((unsigned)((total + LY_THREADS - 1) / LY_THREADS)), dim3(LY_THREADS), 0,
+                                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const T*>(y), ldy, total, H, W, na, no, anchors, stride, p, z, zrows, zoff));
+  LY_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ly_detect_tail_aug(const void* y, int ldy, int n_img, int H, int W, int na, int no, const float* anchors, float stride,
+                                  float* p, float* z, long zrows, long zoff, float dscale, int dflip, float img_w, int dtype, void* stream) {
+  LY_CHECK_DTYPE(dtype, "detect_tail_aug");
+  LY_CHECK(y && z && anchors && dscale > 0.f, "detect_tail_aug: null pointer / bad descale");
+  const long total = (long)n_img * na * H * W * no;
+  LY_WITH_T(dtype, hipLaunchKernelGGL(ly_detect_tail_aug_kernel<T>, dim3((unsigned)((total + LY_THREADS - 1) / LY_THREADS)), dim3(LY_THREADS), 0,
+                                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const T*>(y), ldy, total, H, W, na, no, anchors, stride, p, z,
+                                      zrows, zoff, dscale, dflip, img_w));
+  LY_LAUNCH_CHECK();
+  return 0;
+}
+
+// Adjoint of the raw-map permute above for the training step (models/yolo.py:88 `x[i].view(bs, na, no, ny, nx).permute(0, 1, 3, 4, 2)`):
+// dp fp32 [n, na, H, W, no] -> du rows [n*H*W][ldu] of T (columns a*no + o, columns >= na*no zero: the operand of the head's dgrad /
+// wgrad contractions), and dbias[a*no + o] += sum over pixels.  One launch instead of autograd's cast + two layout copies + zero-padded
+// copy + a reduction.  A block walks (image, row) pairs: the na runs of W*no contiguous floats are staged in LDS, written back as
+// whole rows, and the column sums are kept in registers until one atomic per column and block.
+#define LY_DH_MAXW 160
+#define LY_DH_MAXLD 32
+#define LY_DH_TILE 12288                                   // floats of the LDS tile (48 KB): RB image rows of W pixels x (ldu + 1); >= MAXW * (MAXLD + 1)
+// RB image rows per trip (as many as fit the tile, at most 8): one trip's loads are all in flight together — with one row per trip a block
+// of the 80 x 80 level paid a dependent global -> LDS -> global round trip and two barriers per 5.6 KB — and the rows leave as 8-byte
+// vectors (were 2-byte element stores).
+template <typename T>
+__global__ __launch_bounds__(LY_THREADS) void ly_detect_head_bwd_kernel(const float* __restrict__ dp, int n_img, int H, int W, int na, int no,
+                                                                        T* __restrict__ du, int ldu, float* __restrict__ dbias, const int f64, const int RB) {
+  __shared__ float tile[LY_DH_TILE];
+  __shared__ float red[LY_THREADS];
+  const int tid = threadIdx.x, co = na * no, LT = ldu + 1;
+  const int col = tid & 31, part = tid >> 5;              // column sums: 8 row classes x 32 columns
+  float bsum = 0.f;
+  for (int i = tid; i < RB * W * LT; i += LY_THREADS) tile[i] = 0.f;      // pad columns stay zero
+  const long rows_total = (long)n_img * H;
+  const int q4 = ldu >> 2;                                // 4-element groups of an output row (ldu % 4 == 0: checked by the launcher)
+  for (long r0 = (long)blockIdx.x * RB; r0 < rows_total; r0 += (long)gridDim.x * RB) {
+    const int nr = rows_total - r0 < RB ? (int)(rows_total - r0) : RB;
+    __syncthreads();
+    // one CELL (image row, anchor, pixel: `no` contiguous floats) per thread and step: its index arithmetic is done once, not per value (the
+    // per-value form spent ~30 instructions of divisions on each 4-byte load: 43 us for the 80 x 80 level's 49 MB); no even: 8-byte loads
+    const int cells = nr * na * W;
+    for (int e = tid; e < cells; e += LY_THREADS) {
+      const int rr = e / (na * W), e1 = e - rr * (na * W);
+      const int a = e1 / W, w = e1 - a * W;
+      const long r = r0 + rr;
+      const long n = r / H;
+      const int h = (int)(r - n * H);
+      const float* const src = dp + ((((n * na + a) * H + h) * (long)W) + w) * no;
+      float* const dst = tile + (rr * W + w) * LT + a * no;
+      if ((no & 1) == 0) {
+        for (int o = 0; o < no; o += 2) {
+          const float2 v = *reinterpret_cast<const float2*>(src + o);
+          dst[o] = v.x;
+          dst[o + 1] = v.y;
+        }
+      } else {
+        for (int o = 0; o < no; ++o) dst[o] = src[o];
+      }
+    }
+    __syncthreads();
+    T* const out = du + r0 * (long)W * ldu;               // the nr rows are contiguous in du
+    for (int e = tid; e < nr * W * q4; e += LY_THREADS) {
+      const int px = e / q4, g = e - px * q4;
+      const float* t = tile + px * LT + 4 * g;
+      ly_st4<T>(out + (long)px * ldu + 4 * g, (f32x4){t[0], t[1], t[2], t[3]});
+    }
+    if (col < co)
+      for (int px = part; px < nr * W; px += LY_THREADS / 32) bsum += tile[px * LT + col];
+  }
+  red[tid] = bsum;
+  __syncthreads();
+  if (tid < 32 && tid < co) {
+    float s = 0.f;
+    for (int g = 0; g < LY_THREADS / 32; ++g) s += red[g * 32 + tid];
+    ly_gacc(dbias, tid, s, f64);
+  }
+}
+
+extern "C" int ly_detect_head_bwd(const float* dp, int n_img, int H, int W, int na, int no, void* du, int ldu, float* dbias, int dbias_f64, int dtype,
+                                  void* stream) {
+  LY_CHECK_DTYPE(dtype, "detect_head_bwd");
+  LY_CHECK(dp && du && dbias && n_img > 0 && H > 0 && W > 0 && na > 0 && no > 0 && ((uintptr_t)dp & 7) == 0, "detect_head_bwd: bad arguments");
+  LY_CHECK(W <= LY_DH_MAXW && ldu <= LY_DH_MAXLD && na * no <= ldu && (ldu & 3) == 0 && ((uintptr_t)du & 15) == 0,
+           "detect_head_bwd: W=%d (max %d) / ldu=%d (max %d, >= na*no=%d, a multiple of 4) out of range", W, LY_DH_MAXW, ldu, LY_DH_MAXLD, na * no);
+  int RB = LY_DH_TILE / (W * (ldu + 1));
+  if (RB > 8) RB = 8;
+  long blocks = ((long)n_img * H + RB - 1) / RB;
+  if (blocks > 1024) blocks = 1024;
+  LY_WITH_T(dtype, hipLaunchKernelGGL(ly_detect_head_bwd_kernel<T>, dim3((unsigned)blocks), dim3(LY_THREADS), 0, reinterpret_cast<hipStream_t>(stream), dp,
+                                      n_img, H, W, na, no, reinterpret_cast<T*>(du), ldu, dbias, dbias_f64, RB));
+  LY_LAUNCH_CHECK();
+  return 0;
 }

@@ -3,7 +3,7 @@
 // The depthwise `generate` conv produces, per output pixel p and input channel c, nine values (one per tap t)
 //      v[p, t, c] = sum_u Wd[c, t, u] * x[patch(p, u), c]              (81 MAC per pixel and channel)
 // that the reference materialises as a 9x expanded tensor.  Every kernel of this family REGENERATES them on chip.  The first
-// generation of kernels (ly_rfcbam3.hip, ly_attention.hip) mapped lanes to pixels, which makes the 81 weights of a channel
+// generation of kernels (ly_rfcbam3.hip, ly_rfcbam_att.hip) mapped lanes to pixels, which makes the 81 weights of a channel
 // wave-uniform: they came out of LDS as broadcast reads and the LDS pipe, not the VALU, set the time.  Here
 //      lane = channel (32 channels x 2 pixel streams per wave),
 // so the 81 weights (+ 9 folded biases) of the lane's channel sit in 92 registers for a whole 32-channel chunk, the x patch is

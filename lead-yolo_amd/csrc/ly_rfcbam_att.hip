@@ -1,103 +1,19 @@
-// Small reduction / gating kernels of the two attention blocks (gfx950; activations T = float / __bf16, tables fp32).  All are
-// bandwidth-trivial next to the convolutions; they exist so that the big tensors are read a minimal
-// number of times and the 9x-expanded RFCBAM tensor is never written.
+// The attention side of RFCBAMConv (models/rfa.py:78-127) and its SE block, everything but the main contraction, gfx950: activations
+// T = float / __bf16, tables fp32, moments double.  All are bandwidth-trivial next to the convolutions; they exist so that the big tensors are
+// read a minimal number of times and the 9x-expanded RFCBAM tensor is never written.
 //
-//   ly_pool_hw        CoordAtt pool_h / pool_w               (models/common.py:1598-1599)
-//   ly_coordatt_mlp   conv1+bn1+h_swish, conv_h/conv_w+sigmoid (models/common.py:1600-1607)
-//   ly_colsum         spatial sum per (image, channel)       (SE gap, models/rfa.py:90)
-//   ly_se_mlp         sigmoid(Wb relu(Wa mean))              (models/rfa.py:78-92)
-//   ly_rfcbam_stats   max_c / mean_c of relu(bn(generate(x))) on the expanded grid (models/rfa.py:115-126)
-//   ly_rfa_map        sigmoid(conv3x3([max, mean]))          (models/rfa.py:107,127)
+//   ly_colsum                  spatial sum per (image, channel, slice)                        (SE gap, models/rfa.py:90)
+//   ly_se_fwd                  ly_colsum + sigmoid(Wb relu(Wa mean))                          (models/rfa.py:78-92)
+//   ly_se_bwd                  the same under autograd; dgap for ly_rf_bwd_dx                 (models/rfa.py:88-92)
+//   ly_rfcbam_stats (+ _describe)  max_c / mean_c of relu(bn(generate(x))) on the expanded grid, k = 1 with the SE partials   (models/rfa.py:115-126)
+//   ly_rfa_map                 sigmoid(conv3x3([max, mean]))                                  (models/rfa.py:107,127)
+//   ly_rfcbam_mid              the SE step and ly_rfa_map as one launch (they share ly_se_mlp_body / ly_se_lds_floats with ly_se_fwd)
+//   ly_rfcbam_tap_moments (+ _describe)  train mode, k = 3: the 9 + 45 tap moments per channel behind generate's BatchNorm statistics
+//   ly_rfcbam_gen_prepare      train mode: moments -> generate's BatchNorm coefficients, running stats and folded weights   (models/rfa.py:101-106)
 #include <float.h>
 
 #include "ly_tile.hpp"
 #include "ly_params.h"
-
-
-// ---------------------------------------------------------------------------------------------------
-// generic strided reduction:  out[o, c] = scale * sum_{j < L} x[base(o) + j*stride + c]
-// one block per output row o; threads = (c4, j-lane)
-// ---------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(LY_THREADS) void ly_pool_hw_kernel(const T* __restrict__ x, int ldx, int H, int W, int C,
-                                                                 float* __restrict__ pool) {
-  // block b -> (n, pos); pos < H: mean over w of row pos; else mean over h of column pos-H
-  __shared__ f32x4 red[LY_THREADS];
-  const int L = H + W;
-  const int bid = ly_xcd_remap((int)blockIdx.x, (int)gridDim.x);     // an image's H row blocks and W column blocks read the same cache lines: one XCD's L2
-  const int n = bid / L, pos = bid - n * L;
-  const int nc4 = C >> 2;
-  const int tid = threadIdx.x;
-  const int groups = LY_THREADS / nc4;
-  const bool row = pos < H;
-  const int len = row ? W : H;
-  const long base = row ? ((long)n * H + pos) * W : ((long)n * H) * W + (pos - H);
-  const long step = row ? 1 : W;
-  const int c4 = tid % nc4, j0 = tid / nc4;       // C <= 1024 so nc4 <= 256
-  f32x4 s = ly_zero4();
-  if (j0 < groups) {
-#pragma unroll 4
-    for (int j = j0; j < len; j += groups) s += ly_ld4<T>(x + (base + j * step) * ldx + 4 * c4);
-  }
-  red[tid] = s;
-  __syncthreads();
-  if (j0 == 0) {
-    for (int g = 1; g < groups; ++g) s += red[g * nc4 + c4];
-    const float inv = 1.f / (float)len;
-    ly_stg4(pool + ((long)n * L + pos) * C + 4 * c4, s * inv);
-  }
-}
-
-extern "C" int ly_pool_hw(const void* x, int ldx, int n_img, int H, int W, int C, float* pool, int dtype, void* stream) {
-  LY_CHECK_DTYPE(dtype, "pool_hw");
-  LY_CHECK(x && pool && (C & 3) == 0 && (ldx & 3) == 0 && C <= 1024, "pool_hw: bad arguments (C=%d ldx=%d)", C, ldx);
-  LY_WITH_T(dtype, hipLaunchKernelGGL(ly_pool_hw_kernel<T>, dim3(n_img * (H + W)), dim3(LY_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
-                                      reinterpret_cast<const T*>(x), ldx, H, W, C, pool));
-  LY_LAUNCH_CHECK();
-  return 0;
-}
-
-// y = hswish(W1' pool + b1')  (BN folded),  a = sigmoid(Wx y + bx);  one block per (n, pos)
-__global__ __launch_bounds__(LY_THREADS) void ly_coordatt_mlp_kernel(const float* __restrict__ pool, int H, int W, int C, int mip,
-                                                                      const float* __restrict__ w1, const float* __restrict__ b1,
-                                                                      const float* __restrict__ sc, const float* __restrict__ sh,
-                                                                      const float* __restrict__ wh, const float* __restrict__ bh,
-                                                                      const float* __restrict__ ww, const float* __restrict__ bw,
-                                                                      float* __restrict__ a_h, float* __restrict__ a_w) {
-  __shared__ float ys[64];
-  const int L = H + W;
-  const int n = blockIdx.x / L, pos = blockIdx.x - n * L;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* p = pool + ((long)n * L + pos) * C;
-  for (int m = wave; m < mip; m += 4) {
-    float s = 0.f;
-    for (int c = lane; c < C; c += 64) s += w1[m * C + c] * p[c];
-    s = ly_group_sum(s, 64);
-    if (lane == 0) ys[m] = ly_hswish(sc ? (s + b1[m]) * sc[m] + sh[m] : s + b1[m]);
-  }
-  __syncthreads();
-  const bool isrow = pos < H;
-  const float* wx = isrow ? wh : ww;
-  const float* bx = isrow ? bh : bw;
-  float* out = isrow ? a_h + ((long)n * H + pos) * C : a_w + ((long)n * W + (pos - H)) * C;
-  for (int c = tid; c < C; c += LY_THREADS) {
-    float s = bx[c];
-    for (int m = 0; m < mip; ++m) s += wx[c * mip + m] * ys[m];
-    out[c] = ly_sigmoid(s);
-  }
-}
-
-extern "C" int ly_coordatt_mlp(const float* pool, int n_img, int H, int W, int C, int mip, const float* w1, const float* b1,
-                               const float* sc, const float* sh, const float* wh, const float* bh, const float* ww, const float* bw, float* a_h, float* a_w,
-                               void* stream) {
-  LY_CHECK(pool && w1 && b1 && wh && bh && ww && bw && a_h && a_w && (!sc == !sh), "coordatt_mlp: null pointer");
-  LY_CHECK(mip > 0 && mip <= 64, "coordatt_mlp: mip=%d out of range", mip);
-  hipLaunchKernelGGL(ly_coordatt_mlp_kernel, dim3(n_img * (H + W)), dim3(LY_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
-                     pool, H, W, C, mip, w1, b1, sc, sh, wh, bh, ww, bw, a_h, a_w);
-  LY_LAUNCH_CHECK();
-  return 0;
-}
-
 // ---------------------------------------------------------------------------------------------------
 // SE: partial spatial sums then the two tiny linears
 // ---------------------------------------------------------------------------------------------------
@@ -730,476 +646,6 @@ extern "C" int ly_rfa_map(const float* mm, int n_img, int HK, int WK, const floa
   return 0;
 }
 
-// standalone CoordAtt gating: out = x * a_w[n,w,:] * a_h[n,h,:] (+ res)   (models/common.py:1608, 1623)
-// One block per (image, band of 8 rows, slab of columns); a thread owns a 16-byte channel vector of up to 8 columns: their a_w factors are
-// loaded once, a row's a_h factor once per row, and each row's x (+ res) vectors are all requested before the first use — per 16 bytes of the
-// map one load and one store.  (The first version — thread = (pixel, 4 channels), three 64-bit divisions and two fp32 table loads per 8 bytes
-// of x — ran at 2.4 TB/s.)
-#define LY_GT_RB 8
-#define LY_GT_MAXW 8
-template <typename T>
-__global__ __launch_bounds__(LY_THREADS) void ly_gate_kernel(const T* __restrict__ x, int ldx, int H, int W, int C,
-                                                              const float* __restrict__ a_h, const float* __restrict__ a_w,
-                                                              const T* __restrict__ res, int ldres, T* __restrict__ out, int ldo, int bands, int slabs, int cpt) {
-  constexpr int VW = LyT<T>::VW, NQ = VW / 4;
-  using RV = typename LyT<T>::RV;
-  const int ncv = C / VW, tid = threadIdx.x;
-  const int groups = LY_THREADS / ncv;
-  const int cv = tid % ncv, g0 = tid / ncv;
-  if (g0 >= groups) return;
-  const int slab = blockIdx.x % slabs;
-  const int bb = blockIdx.x / slabs;
-  const long n = bb / bands;
-  const int band = bb - (int)n * bands;
-  const int w0 = slab * groups * cpt;
-  const int h_lo = band * LY_GT_RB, h_hi = h_lo + LY_GT_RB < H ? h_lo + LY_GT_RB : H;
-  const int c = VW * cv;
-  f32x4 aw[LY_GT_MAXW][NQ];
-  bool okw[LY_GT_MAXW];
-  int wcl[LY_GT_MAXW];
-#pragma unroll
-  for (int i = 0; i < LY_GT_MAXW; ++i) {
-    const int w = w0 + g0 + i * groups;
-    okw[i] = i < cpt && w < W;
-    wcl[i] = okw[i] ? w : (w0 < W ? w0 : 0);
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) aw[i][q] = ly_ldg4(a_w + (n * W + wcl[i]) * C + c + 4 * q);
-  }
-  for (int h = h_lo; h < h_hi; ++h) {
-    const long nh = n * H + h;
-    f32x4 ah[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) ah[q] = ly_ldg4(a_h + nh * C + c + 4 * q);
-    RV xr[LY_GT_MAXW], rr[LY_GT_MAXW];
-#pragma unroll
-    for (int i = 0; i < LY_GT_MAXW; ++i) {
-      if (i >= cpt) break;                                                     // (uniform: columns per thread of this launch)
-      const long row = nh * W + wcl[i];
-      xr[i] = ly_ldrv<T>(x + row * ldx + c);
-      if (res) rr[i] = ly_ldrv<T>(res + row * ldres + c);
-    }
-#pragma unroll
-    for (int i = 0; i < LY_GT_MAXW; ++i) {
-      if (i >= cpt) break;
-      f32x4 v[NQ], r[NQ];
-      ly_rv_unpack(xr[i], v);
-      if (res) ly_rv_unpack(rr[i], r);
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) {
-        v[q] = v[q] * aw[i][q] * ah[q];
-        if (res) v[q] += r[q];
-      }
-      if (okw[i]) *reinterpret_cast<RV*>(out + (nh * W + wcl[i]) * ldo + c) = ly_rv_pack(v, (RV*)nullptr);
-    }
-  }
-}
-
-extern "C" int ly_coordatt_gate(const void* x, int ldx, int n_img, int H, int W, int C, const float* a_h, const float* a_w,
-                                const void* res, int ldres, void* out, int ldo, int dtype, void* stream) {
-  LY_CHECK_DTYPE(dtype, "gate");
-  const int vw = dtype == LY_BF16 ? 8 : 4;
-  LY_CHECK(x && a_h && a_w && out && (C % vw) == 0 && (ldx % vw) == 0 && (ldo % vw) == 0 && (ldres % vw) == 0 && C / vw <= LY_THREADS,
-           "gate: C = %d and the row strides must be multiples of %d (16-byte channel vectors)", C, vw);
-  const int groups = LY_THREADS / (C / vw);
-  int cpt = (W + groups - 1) / groups;
-  if (cpt > LY_GT_MAXW) cpt = LY_GT_MAXW;
-  const int slabs = (W + groups * cpt - 1) / (groups * cpt);
-  const int bands = (H + LY_GT_RB - 1) / LY_GT_RB;
-  LY_WITH_T(dtype, hipLaunchKernelGGL(ly_gate_kernel<T>, dim3((unsigned)((long)n_img * bands * slabs)), dim3(LY_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
-                                      reinterpret_cast<const T*>(x), ldx, H, W, C, a_h, a_w, reinterpret_cast<const T*>(res), ldres, reinterpret_cast<T*>(out), ldo,
-                                      bands, slabs, cpt));
-  LY_LAUNCH_CHECK();
-  return 0;
-}
-
-
-// ---------------------------------------------------------------------------------------------------
-// SPPF pooling: out[n, p, 0:C] = x, [C:2C] = m5(x), [2C:3C] = m5(m5(x)), [3C:4C] = m5(m5(m5(x)))
-// (k x k, stride 1, pad k//2, -inf padding; reference models/common.py:348-366).  Chained k-max pools
-// equal single (2k-1)- and (3k-2)-wide max windows, computed separably from one LDS copy of the map.
-// One block per (image, 16-channel group); the map (H*W <= 4096) lives in LDS.
-// ---------------------------------------------------------------------------------------------------
-#define LY_SP_CG 4     // channels per block: n_img * C/4 blocks keep the whole chip busy on the small P5 map
-template <typename T>
-__global__ __launch_bounds__(LY_THREADS) void ly_sppf_pool_kernel(const T* __restrict__ x, int ldx, int H, int W, int C, int k,
-                                                                  T* __restrict__ out, int ldo) {
-  extern __shared__ f32x4 sp4[];               // a[HW], b[HW] as float4 (4 channels per position)
-  const int HW = H * W;
-  f32x4* a = sp4;
-  f32x4* b = sp4 + HW;
-  const int groups = C / LY_SP_CG;
-  const int bid = ly_xcd_remap((int)blockIdx.x, (int)gridDim.x);
-  const int n = bid / groups, g = bid - n * groups;
-  const int c0 = g * LY_SP_CG;
-  const int tid = threadIdx.x, r = k / 2;
-  const f32x4 ninf = (f32x4){-FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
-  for (int p = tid; p < HW; p += LY_THREADS) {
-    const f32x4 v = ly_ld4<T>(x + ((long)n * HW + p) * ldx + c0);
-    a[p] = v;
-    ly_st4<T>(out + ((long)n * HW + p) * ldo + c0, v);
-  }
-  __syncthreads();
-  for (int level = 1; level <= 3; ++level) {
-    // b = row-max of a, then a = col-max of b  (one k x k max pool of the previous level)
-    for (int p = tid; p < HW; p += LY_THREADS) {
-      const int h = p / W, w = p - h * W;
-      f32x4 m = ninf;
-      for (int d = -r; d <= r; ++d) {
-        const int ww = w + d;
-        if (ww >= 0 && ww < W) {
-          const f32x4 v = a[h * W + ww];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) m[q] = fmaxf(m[q], v[q]);
-        }
-      }
-      b[p] = m;
-    }
-    __syncthreads();
-    for (int p = tid; p < HW; p += LY_THREADS) {
-      const int h = p / W, w = p - h * W;
-      f32x4 m = ninf;
-      for (int d = -r; d <= r; ++d) {
-        const int hh = h + d;
-        if (hh >= 0 && hh < H) {
-          const f32x4 v = b[hh * W + w];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) m[q] = fmaxf(m[q], v[q]);
-        }
-      }
-      a[p] = m;
-      ly_st4<T>(out + ((long)n * HW + p) * ldo + level * C + c0, m);
-    }
-    __syncthreads();
-  }
-}
-
-extern "C" int ly_sppf_pool(const void* x, int ldx, int n_img, int H, int W, int C, int k, void* out, int ldo, int dtype, void* stream) {
-  LY_CHECK_DTYPE(dtype, "sppf_pool");
-  LY_CHECK(x && out && k >= 1 && (k & 1) && (C & 3) == 0 && (ldx & 3) == 0 && (ldo & 3) == 0, "sppf_pool: bad arguments");
-  size_t lds = sizeof(float) * 2 * (size_t)H * W * 4;
-  LY_CHECK(lds <= LY_LDS_MAX, "sppf_pool: %dx%d map does not fit LDS (%zu B)", H, W, lds);
-  LY_WITH_T(dtype, return ly_launch_lds<ly_sppf_pool_kernel<T>>(dim3(n_img * (C / LY_SP_CG)), dim3(LY_THREADS), lds, reinterpret_cast<hipStream_t>(stream),
-                                                                reinterpret_cast<const T*>(x), ldx, H, W, C, k, reinterpret_cast<T*>(out), ldo));
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Detect tail (reference models/yolo.py:95-120): from the head GEMM output y[n, h, w, na*no] (row stride
-// ldy) write the raw map p[n, a, h, w, o] and, in eval mode, the decoded rows z[n, zoff + (a*H + h)*W + w, o]:
-//   xy = (2*sig - 0.5 + grid) * stride,  wh = (2*sig)^2 * anchor*stride,  rest = sig.
-// ---------------------------------------------------------------------------------------------------
-// AUG: the _descale_pred step of test-time augmentation on the decoded rows (see ly_detect_level_body in ly_detect.hip); p may be NULL there.
-template <typename T, bool AUG>
-__device__ __forceinline__ void ly_detect_tail_body(const T* __restrict__ y, int ldy, long total, int H, int W, int na, int no,
-                                                    const float* __restrict__ anchors /* [na,2] grid units */, float stride,
-                                                    float* __restrict__ p, float* __restrict__ z, long zrows, long zoff, float dscale, int dflip,
-                                                    float img_w) {
-  const long i = (long)blockIdx.x * LY_THREADS + threadIdx.x;      // over n*na*H*W*no, output order
-  if (i >= total) return;
-  const int o = (int)(i % no);
-  long t = i / no;
-  const int w = (int)(t % W); t /= W;
-  const int h = (int)(t % H); t /= H;
-  const int a = (int)(t % na);
-  const long n = t / na;
-  const float v = ly_ld1<T>(y + ((n * H + h) * W + w) * ldy + a * no + o);
-  if constexpr (AUG) {
-    if (p) p[i] = v;
-  } else {
-    p[i] = v;
-  }
-  if (z) {
-    const float s = ly_sigmoid(v);
-    float r = s;
-    if (o == 0) r = (s * 2.f + ((float)w - 0.5f)) * stride;
-    else if (o == 1) r = (s * 2.f + ((float)h - 0.5f)) * stride;
-    else if (o == 2 || o == 3) { const float q = s * 2.f; r = q * q * (anchors[a * 2 + (o - 2)] * stride); }
-    if constexpr (AUG) {
-      if (o < 4) r = r / dscale;
-      if (o == 0 && dflip) r = img_w - r;
-    }
-    z[(n * zrows + zoff + ((long)a * H + h) * W + w) * no + o] = r;
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(LY_THREADS) void ly_detect_tail_kernel(const T* __restrict__ y, int ldy, long total, int H, int W, int na, int no,
-                                                                    const float* __restrict__ anchors /* [na,2] grid units */, float stride,
-                                                                    float* __restrict__ p, float* __restrict__ z, long zrows, long zoff) {
-  ly_detect_tail_body<T, false>(y, ldy, total, H, W, na, no, anchors, stride, p, z, zrows, zoff, 1.f, 0, 0.f);
-}
-
-template <typename T>
-__global__ __launch_bounds__(LY_THREADS) void ly_detect_tail_aug_kernel(const T* __restrict__ y, int ldy, long total, int H, int W, int na, int no,
-                                                                        const float* __restrict__ anchors, float stride, float* __restrict__ p,
-                                                                        float* __restrict__ z, long zrows, long zoff, float dscale, int dflip, float img_w) {
-  ly_detect_tail_body<T, true>(y, ldy, total, H, W, na, no, anchors, stride, p, z, zrows, zoff, dscale, dflip, img_w);
-}
-
-extern "C" int ly_detect_tail(const void* y, int ldy, int n_img, int H, int W, int na, int no, const float* anchors, float stride,
-                              float* p, float* z, long zrows, long zoff, int dtype, void* stream) {
-  LY_CHECK_DTYPE(dtype, "detect_tail");
-  LY_CHECK(y && p && anchors, "detect_tail: null pointer");
-  const long total = (long)n_img * na * H * W * no;
-  LY_WITH_T(dtype, hipLaunchKernelGGL(ly_detect_tail_kernel<T>, dim3((unsigned)((total + LY_THREADS - 1) / LY_THREADS)), dim3(LY_THREADS), 0,
-                                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const T*>(y), ldy, total, H, W, na, no, anchors, stride, p, z, zrows, zoff));
-  LY_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int ly_detect_tail_aug(const void* y, int ldy, int n_img, int H, int W, int na, int no, const float* anchors, float stride,
-                                  float* p, float* z, long zrows, long zoff, float dscale, int dflip, float img_w, int dtype, void* stream) {
-  LY_CHECK_DTYPE(dtype, "detect_tail_aug");
-  LY_CHECK(y && z && anchors && dscale > 0.f, "detect_tail_aug: null pointer / bad descale");
-  const long total = (long)n_img * na * H * W * no;
-  LY_WITH_T(dtype, hipLaunchKernelGGL(ly_detect_tail_aug_kernel<T>, dim3((unsigned)((total + LY_THREADS - 1) / LY_THREADS)), dim3(LY_THREADS), 0,
-                                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const T*>(y), ldy, total, H, W, na, no, anchors, stride, p, z,
-                                      zrows, zoff, dscale, dflip, img_w));
-  LY_LAUNCH_CHECK();
-  return 0;
-}
-
-// Adjoint of the raw-map permute above for the training step (models/yolo.py:88 `x[i].view(bs, na, no, ny, nx).permute(0, 1, 3, 4, 2)`):
-// dp fp32 [n, na, H, W, no] -> du rows [n*H*W][ldu] of T (columns a*no + o, columns >= na*no zero: the operand of the head's dgrad /
-// wgrad contractions), and dbias[a*no + o] += sum over pixels.  One launch instead of autograd's cast + two layout copies + zero-padded
-// copy + a reduction.  A block walks (image, row) pairs: the na runs of W*no contiguous floats are staged in LDS, written back as
-// whole rows, and the column sums are kept in registers until one atomic per column and block.
-#define LY_DH_MAXW 160
-#define LY_DH_MAXLD 32
-#define LY_DH_TILE 12288                                   // floats of the LDS tile (48 KB): RB image rows of W pixels x (ldu + 1); >= MAXW * (MAXLD + 1)
-// RB image rows per trip (as many as fit the tile, at most 8): one trip's loads are all in flight together — with one row per trip a block
-// of the 80 x 80 level paid a dependent global -> LDS -> global round trip and two barriers per 5.6 KB — and the rows leave as 8-byte
-// vectors (were 2-byte element stores).
-template <typename T>
-__global__ __launch_bounds__(LY_THREADS) void ly_detect_head_bwd_kernel(const float* __restrict__ dp, int n_img, int H, int W, int na, int no,
-                                                                        T* __restrict__ du, int ldu, float* __restrict__ dbias, const int f64, const int RB) {
-  __shared__ float tile[LY_DH_TILE];
-  __shared__ float red[LY_THREADS];
-  const int tid = threadIdx.x, co = na * no, LT = ldu + 1;
-  const int col = tid & 31, part = tid >> 5;              // column sums: 8 row classes x 32 columns
-  float bsum = 0.f;
-  for (int i = tid; i < RB * W * LT; i += LY_THREADS) tile[i] = 0.f;      // pad columns stay zero
-  const long rows_total = (long)n_img * H;
-  const int run = W * no;
-  const int q4 = ldu >> 2;                                // 4-element groups of an output row (ldu % 4 == 0: checked by the launcher)
-  for (long r0 = (long)blockIdx.x * RB; r0 < rows_total; r0 += (long)gridDim.x * RB) {
-    const int nr = rows_total - r0 < RB ? (int)(rows_total - r0) : RB;
-    __syncthreads();
-    // one CELL (image row, anchor, pixel: `no` contiguous floats) per thread and step: its index arithmetic is done once, not per value (the
-    // per-value form spent ~30 instructions of divisions on each 4-byte load: 43 us for the 80 x 80 level's 49 MB); no even: 8-byte loads
-    const int cells = nr * na * W;
-    for (int e = tid; e < cells; e += LY_THREADS) {
-      const int rr = e / (na * W), e1 = e - rr * (na * W);
-      const int a = e1 / W, w = e1 - a * W;
-      const long r = r0 + rr;
-      const long n = r / H;
-      const int h = (int)(r - n * H);
-      const float* const src = dp + ((((n * na + a) * H + h) * (long)W) + w) * no;
-      float* const dst = tile + (rr * W + w) * LT + a * no;
-      if ((no & 1) == 0) {
-        for (int o = 0; o < no; o += 2) {
-          const float2 v = *reinterpret_cast<const float2*>(src + o);
-          dst[o] = v.x;
-          dst[o + 1] = v.y;
-        }
-      } else {
-        for (int o = 0; o < no; ++o) dst[o] = src[o];
-      }
-    }
-    __syncthreads();
-    T* const out = du + r0 * (long)W * ldu;               // the nr rows are contiguous in du
-    for (int e = tid; e < nr * W * q4; e += LY_THREADS) {
-      const int px = e / q4, g = e - px * q4;
-      const float* t = tile + px * LT + 4 * g;
-      ly_st4<T>(out + (long)px * ldu + 4 * g, (f32x4){t[0], t[1], t[2], t[3]});
-    }
-    if (col < co)
-      for (int px = part; px < nr * W; px += LY_THREADS / 32) bsum += tile[px * LT + col];
-  }
-  red[tid] = bsum;
-  __syncthreads();
-  if (tid < 32 && tid < co) {
-    float s = 0.f;
-    for (int g = 0; g < LY_THREADS / 32; ++g) s += red[g * 32 + tid];
-    ly_gacc(dbias, tid, s, f64);
-  }
-}
-
-extern "C" int ly_detect_head_bwd(const float* dp, int n_img, int H, int W, int na, int no, void* du, int ldu, float* dbias, int dbias_f64, int dtype,
-                                  void* stream) {
-  LY_CHECK_DTYPE(dtype, "detect_head_bwd");
-  LY_CHECK(dp && du && dbias && n_img > 0 && H > 0 && W > 0 && na > 0 && no > 0 && ((uintptr_t)dp & 7) == 0, "detect_head_bwd: bad arguments");
-  LY_CHECK(W <= LY_DH_MAXW && ldu <= LY_DH_MAXLD && na * no <= ldu && (ldu & 3) == 0 && ((uintptr_t)du & 15) == 0,
-           "detect_head_bwd: W=%d (max %d) / ldu=%d (max %d, >= na*no=%d, a multiple of 4) out of range", W, LY_DH_MAXW, ldu, LY_DH_MAXLD, na * no);
-  int RB = LY_DH_TILE / (W * (ldu + 1));
-  if (RB > 8) RB = 8;
-  long blocks = ((long)n_img * H + RB - 1) / RB;
-  if (blocks > 1024) blocks = 1024;
-  LY_WITH_T(dtype, hipLaunchKernelGGL(ly_detect_head_bwd_kernel<T>, dim3((unsigned)blocks), dim3(LY_THREADS), 0, reinterpret_cast<hipStream_t>(stream), dp,
-                                      n_img, H, W, na, no, reinterpret_cast<T*>(du), ldu, dbias, dbias_f64, RB));
-  LY_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Train-mode BatchNorm support kernels (statistics passes; normalisation itself is folded into the
-// consumers' scale/shift exactly like the eval path)
-// ---------------------------------------------------------------------------------------------------
-// per-channel sum / sum of squares over all rows of an [rows, C] matrix: mom[c] += sum x, mom[C + c] += sum x^2
-template <typename T>
-__global__ __launch_bounds__(LY_THREADS) void ly_chan_moments_kernel(const T* __restrict__ x, int ldx, long rows, int C,
-                                                                      double* __restrict__ mom) {
-  __shared__ f32x4 red1[LY_THREADS], red2[LY_THREADS];
-  const int nc4 = C >> 2, tid = threadIdx.x;
-  const int groups = LY_THREADS / nc4;
-  const int c4 = tid % nc4, j0 = tid / nc4;
-  f32x4 s1 = ly_zero4(), s2 = ly_zero4();
-  if (j0 < groups) {
-    // four rows per trip, all four loads issued before the first use (one row per trip paid a round trip per row: 21 us for the 8 MB of
-    // RFCBAMConv layer 9's input, on 67 blocks); rows past the end re-read the last row and are masked
-    const long step = (long)gridDim.x * groups;
-    for (long r = (long)blockIdx.x * groups + j0; r < rows; r += 4 * step) {
-      f32x4 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const long rr = r + u * step;
-        v[u] = ly_ld4<T>(x + (rr < rows ? rr : rows - 1) * ldx + 4 * c4);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const f32x4 w = r + u * step < rows ? v[u] : ly_zero4();
-        s1 += w;
-        s2 += w * w;
-      }
-    }
-  }
-  red1[tid] = s1; red2[tid] = s2;
-  __syncthreads();
-  if (j0 == 0) {
-    for (int g = 1; g < groups; ++g) { s1 += red1[g * nc4 + c4]; s2 += red2[g * nc4 + c4]; }
-    double* m = mom + (size_t)(blockIdx.x & (LY_STATS_STRIPES - 1)) * 2 * C;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      atomicAdd(m + 4 * c4 + r, (double)s1[r]);
-      atomicAdd(m + C + 4 * c4 + r, (double)s2[r]);
-    }
-  }
-}
-
-extern "C" int ly_chan_moments(const void* x, int ldx, long rows, int C, double* mom, int dtype, void* stream) {
-  LY_CHECK_DTYPE(dtype, "chan_moments");
-  LY_CHECK(x && mom && (C & 3) == 0 && (ldx & 3) == 0 && C <= 1024 && rows > 0, "chan_moments: bad arguments");
-  const int groups = LY_THREADS / (C >> 2);
-  long blocks = (rows + groups * 16L - 1) / (groups * 16L);    // ~16 rows per row group: four trips of four rows in flight
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  LY_WITH_T(dtype, hipLaunchKernelGGL(ly_chan_moments_kernel<T>, dim3((unsigned)blocks), dim3(LY_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
-                                      reinterpret_cast<const T*>(x), ldx, rows, C, mom));
-  LY_LAUNCH_CHECK();
-  return 0;
-}
-
-// CoordAtt bn1 statistics: y1[n, pos, m] = w1[m, :] . pool[n, pos, :] + b1[m];  stats[m] += y1, stats[mip + m] += y1^2
-// One WAVE per position: lanes stride the channels and carry all `mip` outputs (MIPMAX accumulators), one shuffle tree per position,
-// lanes m < mip keep the running sums; the four waves of a block meet in LDS and the block adds ONCE per output.  (The first version
-// gave each wave two outputs and walked the block's positions serially per output: 113 us per launch.)
-template <int MIPMAX>
-__global__ __launch_bounds__(LY_THREADS) void ly_coordatt_conv1_stats_kernel(const float* __restrict__ pool, long positions, int C, int mip,
-                                                                              const float* __restrict__ w1, const float* __restrict__ b1,
-                                                                              double* __restrict__ stats) {
-  __shared__ float red[4][2 * MIPMAX];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  float a1 = 0.f, a2 = 0.f;
-  // the lane that accumulates output m: lane m on the general path; on the fast path the reduce-scatter leaves output m in lane m * (64 / MIPMAX)
-  constexpr bool FASTP = MIPMAX <= 16;
-  constexpr int LSTEP = FASTP ? 64 / MIPMAX : 1;
-  const bool fast = FASTP && C <= 256;
-  const int mine = fast ? lane / LSTEP : lane;
-  const bool owner = (fast ? (lane % LSTEP) == 0 : true) && mine < mip;
-  const float bm = owner ? b1[mine] : 0.f;
-  const long nw = (long)gridDim.x * 4;
-  if constexpr (FASTP) if (fast) {
-    // the lane's weights stay in registers over all positions, and two positions per trip have all their loads issued before the first use
-    // (the one-position loop re-read w1 and paid a dependent round trip per position: 23 us for 2.6 MB)
-    constexpr int KC = 4;
-    float wreg[KC][MIPMAX];
-#pragma unroll
-    for (int k = 0; k < KC; ++k)
-#pragma unroll
-      for (int m = 0; m < MIPMAX; ++m) wreg[k][m] = (m < mip && lane + 64 * k < C) ? w1[m * C + lane + 64 * k] : 0.f;
-    constexpr int UP = 2;
-    for (long pos0 = (long)blockIdx.x * 4 + wave; pos0 < positions; pos0 += UP * nw) {
-      float pv[UP][KC];
-#pragma unroll
-      for (int u = 0; u < UP; ++u) {
-        const long pos = pos0 + u * nw < positions ? pos0 + u * nw : positions - 1;
-#pragma unroll
-        for (int k = 0; k < KC; ++k) pv[u][k] = lane + 64 * k < C ? pool[pos * C + lane + 64 * k] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < UP; ++u) {
-        const bool live = pos0 + u * nw < positions;
-        float y[MIPMAX];
-#pragma unroll
-        for (int m = 0; m < MIPMAX; ++m) {
-          y[m] = 0.f;
-#pragma unroll
-          for (int k = 0; k < KC; ++k) y[m] += wreg[k][m] * pv[u][k];
-        }
-        ly_reduce_scatter<MIPMAX>(y, lane);                 // MIPMAX - 1 + log2(64 / MIPMAX) cross-lane moves instead of 6 MIPMAX
-        if (owner && live) {
-          const float v = y[0] + bm;
-          a1 += v;
-          a2 += v * v;
-        }
-      }
-    }
-  }
-  if (!fast) {
-  for (long pos = (long)blockIdx.x * 4 + wave; pos < positions; pos += nw) {
-    const float* p = pool + pos * C;
-    float y[MIPMAX];
-#pragma unroll
-    for (int m = 0; m < MIPMAX; ++m) y[m] = 0.f;
-    for (int c = lane; c < C; c += 64) {
-      const float pv = p[c];
-#pragma unroll
-      for (int m = 0; m < MIPMAX; ++m)
-        if (m < mip) y[m] += w1[m * C + c] * pv;
-    }
-#pragma unroll
-    for (int m = 0; m < MIPMAX; ++m) {
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) y[m] += __shfl_xor(y[m], o);
-      if (lane == m) {
-        const float v = y[m] + bm;
-        a1 += v;
-        a2 += v * v;
-      }
-    }
-  }
-  }
-  if (owner) { red[wave][mine] = a1; red[wave][MIPMAX + mine] = a2; }
-  __syncthreads();
-  if (wave == 0 && lane < mip) {
-    atomicAdd(stats + lane, (double)((red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane])));
-    atomicAdd(stats + mip + lane, (double)((red[0][MIPMAX + lane] + red[1][MIPMAX + lane]) + (red[2][MIPMAX + lane] + red[3][MIPMAX + lane])));
-  }
-}
-
-extern "C" int ly_coordatt_conv1_stats(const float* pool, long positions, int C, int mip, const float* w1, const float* b1,
-                                       double* stats, void* stream) {
-  LY_CHECK(pool && w1 && b1 && stats && positions > 0 && mip > 0, "coordatt_conv1_stats: bad arguments");
-  LY_CHECK(mip <= 64, "coordatt_conv1_stats: mip=%d out of range", mip);
-  long blocks = (positions + 3) / 4;
-  if (blocks > 256) blocks = 256;                          // one atomic per (block, output): keep the adds per address few
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (mip <= 8) hipLaunchKernelGGL(ly_coordatt_conv1_stats_kernel<8>, dim3((unsigned)blocks), dim3(LY_THREADS), 0, st, pool, positions, C, mip, w1, b1, stats);
-  else if (mip <= 16) hipLaunchKernelGGL(ly_coordatt_conv1_stats_kernel<16>, dim3((unsigned)blocks), dim3(LY_THREADS), 0, st, pool, positions, C, mip, w1, b1, stats);
-  else hipLaunchKernelGGL(ly_coordatt_conv1_stats_kernel<64>, dim3((unsigned)blocks), dim3(LY_THREADS), 0, st, pool, positions, C, mip, w1, b1, stats);
-  LY_LAUNCH_CHECK();
-  return 0;
-}
-
 // RFCBAMConv k=3 `generate` BatchNorm statistics (train mode).  The pre-BN value of channel c, tap-output t at
 // an output pixel is a_t = sum_u w[c,t,u] * x_u with x_u the 9 (zero padded, stride s) input taps of that pixel,
 // so  sum a_t = w_t . m   and   sum a_t^2 = w_t^T M w_t  with  m[u] = sum_pixels x_u,  M[u][v] = sum_pixels x_u x_v.
@@ -1386,220 +832,6 @@ extern "C" int ly_rfcbam_tap_moments(const void* x, int ldx, int n_img, int H, i
 extern "C" int ly_rfcbam_tap_moments_describe(const void* x, int ldx, int n_img, int H, int W, int C, int s, double* mom, int dtype, char* name, int cap) {
   LY_CHECK(name && cap > 0, "rfcbam_tap_moments_describe: bad arguments");
   return tap_moments_entry(x, ldx, n_img, H, W, C, s, mom, dtype, LyOut{nullptr, name, cap});
-}
-
-// ---------------------------------------------------------------------------------------------------
-// CoordAtt vector MLP, training backward (models/common.py:1600-1607 under autograd):
-//   y0 = W1 pool + b1;  xh = (y0 - mean) * invstd;  y1 = gamma*xh + beta;  y2 = h_swish(y1);  a = sigmoid(Wx y2 + bx)
-// with Wx = conv_h for the H row positions of an image and conv_w for its W column positions.  Two launches, because
-// BatchNorm's backward needs sum(dy1) and sum(dy1*xh) over ALL positions before any dy0 exists:
-//   bwd1 (one WAVE per position, lanes stride the channels, both length-C reductions are shuffle trees, nothing synchronises):
-//         dz = da*a*(1-a) -> dpool buffer;  dy1 = (Wx^T dz) * h_swish'(y1);  (dy1, xh, y2) -> ws;  sums += (dy1, dy1*xh)  (striped)
-//   bwd2 (lane = channel, block = 64 channels x a chunk of positions, waves = row phases):
-//         dy0 = gamma*invstd*(dy1 - S1/R - xh*S2/R);  dpool = W1^T dy0 (over dz, in place);  dW1 += dy0 (x) pool;
-//         dWx += dz (x) y2, dbx += dz;  dgamma += S2, dbeta += S1.   (db1 = sum dy0 is identically zero: BatchNorm removes the mean.)
-// Every parameter gradient is summed in registers, then over the block's waves through LDS, and ADDED to its target once per block
-// (a few dozen adds per address: same-address float atomics serialise, ~0.05 us each).
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float ly_hswish_grad(float x) { return x <= -3.f ? 0.f : (x >= 3.f ? 1.f : (2.f * x + 3.f) * (1.f / 6.f)); }
-#define LY_CA_STRIPES 32
-
-template <int MIP, int NS>
-__global__ __launch_bounds__(LY_THREADS) void ly_coordatt_mlp_bwd1_kernel(
-    const float* __restrict__ pool, int n_img, int H, int W, int C, const float* __restrict__ w1, const float* __restrict__ b1,
-    const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta,
-    const float* __restrict__ wh, const float* __restrict__ ww, const float* __restrict__ a_h, const float* __restrict__ a_w,
-    const float* __restrict__ da_h, const float* __restrict__ da_w, float* __restrict__ ws, double* __restrict__ sums, float* __restrict__ dzb) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int L = H + W;
-  const long R = (long)n_img * L;
-  float s1 = 0.f, s2 = 0.f;                                // the lane that owns output m: sum dy1[m], sum dy1[m]*xh[m]
-  static_assert(MIP == 8 || MIP == 16, "ly_coordatt_mlp_bwd1: MIP = 8 or 16");
-  constexpr int LSTEP = 64 / MIP;
-  const int mine = lane / LSTEP;
-  const bool owner = (lane % LSTEP) == 0;
-  const float b1m = b1[mine], meanm = mean[mine], invm = invstd[mine], gm = gamma[mine], bem = beta[mine];
-  const long nw = (long)gridDim.x * 4;
-  for (long r = (long)blockIdx.x * 4 + wave; r < R; r += nw) {
-    const long n = r / L;
-    const int pos = (int)(r - n * L);
-    const bool isrow = pos < H;
-    const long q = isrow ? n * H + pos : n * W + (pos - H);
-    const float* wx = isrow ? wh : ww;
-    const float* am = (isrow ? a_h : a_w) + q * C;
-    const float* dam = (isrow ? da_h : da_w) + q * C;
-    float y[MIP], d[MIP];
-#pragma unroll
-    for (int m = 0; m < MIP; ++m) { y[m] = 0.f; d[m] = 0.f; }
-#pragma unroll
-    for (int sl = 0; sl < NS; ++sl) {
-      const int c = lane + 64 * sl;
-      if (c < C) {
-        const float pv = pool[r * C + c];
-        const float av = am[c];
-        const float dz = dam[c] * av * (1.f - av);
-        dzb[r * C + c] = dz;
-#pragma unroll
-        for (int m = 0; m < MIP; ++m) {
-          y[m] += w1[m * C + c] * pv;
-          d[m] += dz * wx[c * MIP + m];
-        }
-      }
-    }
-    // both length-C reductions as reduce-scatters (ly_common.hpp): 2 (MIP - 1 + log2(64 / MIP)) cross-lane moves per position instead of 12 MIP;
-    // output m ends up in lane m * (64 / MIP), which keeps its running sums
-    ly_reduce_scatter<MIP>(y, lane);
-    ly_reduce_scatter<MIP>(d, lane);
-    if (owner) {
-      const float xh = (y[0] + b1m - meanm) * invm;
-      const float y1 = gm * xh + bem;
-      const float g = d[0] * ly_hswish_grad(y1);
-      s1 += g;
-      s2 += g * xh;
-      ws[r * 3 * MIP + mine] = g;
-      ws[r * 3 * MIP + MIP + mine] = xh;
-      ws[r * 3 * MIP + 2 * MIP + mine] = ly_hswish(y1);
-    }
-  }
-  if (owner) {
-    double* st = sums + ((blockIdx.x * 4 + wave) & (LY_CA_STRIPES - 1)) * 2 * MIP;      // double accumulators: see ly_stats_flush (ly_common.hpp)
-    atomicAdd(st + mine, (double)s1);
-    atomicAdd(st + MIP + mine, (double)s2);
-  }
-}
-
-template <int MIP>
-__global__ __launch_bounds__(LY_THREADS) void ly_coordatt_mlp_bwd2_kernel(
-    const float* __restrict__ pool, int n_img, int H, int W, int C, long rows_per_block, const float* __restrict__ w1,
-    const float* __restrict__ gamma, const float* __restrict__ invstd, const float* __restrict__ ws, const double* __restrict__ sums,
-    float* __restrict__ dpool /* in: dz */, float* __restrict__ dw1, float* __restrict__ dgamma, float* __restrict__ dbeta,
-    float* __restrict__ dwh, float* __restrict__ dbh, float* __restrict__ dww, float* __restrict__ dbw, const int f64) {
-  constexpr int NA = 3 * MIP + 2;                          // accumulators per channel: dW1[m], dWh[m], dWw[m], dbh, dbw
-  __shared__ float red[4 * 64 * (3 * MIP + 2)];
-  __shared__ float ssum[2 * MIP];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int L = H + W;
-  const long R = (long)n_img * L;
-  const int c = blockIdx.x * 64 + lane;
-  const bool cok = c < C;
-  if (tid < 2 * MIP) {
-    double v = 0.0;
-    for (int st = 0; st < LY_CA_STRIPES; ++st) v += sums[st * 2 * MIP + tid];
-    ssum[tid] = (float)v;
-  }
-  __syncthreads();
-  const float invR = 1.f / (float)R;
-  float k0[MIP], m1[MIP], m2[MIP], w1r[MIP];
-  float acc[NA];
-#pragma unroll
-  for (int m = 0; m < MIP; ++m) {
-    k0[m] = gamma[m] * invstd[m];
-    m1[m] = ssum[m] * invR;
-    m2[m] = ssum[MIP + m] * invR;
-    w1r[m] = cok ? w1[m * C + c] : 0.f;
-  }
-#pragma unroll
-  for (int e = 0; e < NA; ++e) acc[e] = 0.f;
-  const long r_lo = (long)blockIdx.y * rows_per_block;
-  const long r_hi = r_lo + rows_per_block < R ? r_lo + rows_per_block : R;
-  // four rows per trip, every load of the trip issued before the first use (the one-row loop paid a dependent round trip per row: 47 us
-  // for 2.6 MB of pooled vectors); rows past the block's range re-read its last row and are masked
-  constexpr int UR = 4;
-  for (long r0 = r_lo + wave; r0 < r_hi; r0 += 4 * UR) {
-    float pv[UR], dz[UR], wv[UR][3 * MIP];
-    bool live[UR];
-#pragma unroll
-    for (int u = 0; u < UR; ++u) {
-      const long rr = r0 + 4 * u;
-      live[u] = rr < r_hi;
-      const long r = live[u] ? rr : r_hi - 1;
-      const float* wr = ws + r * 3 * MIP;                  // wave-uniform row: (dy1, xh, y2)
-#pragma unroll
-      for (int m = 0; m < 3 * MIP; ++m) wv[u][m] = wr[m];
-      pv[u] = cok ? pool[r * C + c] : 0.f;
-      dz[u] = cok ? dpool[r * C + c] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < UR; ++u) {
-      const long r = r0 + 4 * u;
-      const int pos = (int)(r % L);
-      const bool isrow = pos < H;
-      const float dzu = live[u] ? dz[u] : 0.f, pvu = live[u] ? pv[u] : 0.f;
-      float g = 0.f;
-#pragma unroll
-      for (int m = 0; m < MIP; ++m) {
-        const float dy0 = live[u] ? k0[m] * (wv[u][m] - m1[m] - wv[u][MIP + m] * m2[m]) : 0.f;
-        const float t = dzu * wv[u][2 * MIP + m];
-        g += dy0 * w1r[m];
-        acc[m] += dy0 * pvu;
-        acc[MIP + m] += isrow ? t : 0.f;
-        acc[2 * MIP + m] += isrow ? 0.f : t;
-      }
-      acc[3 * MIP] += isrow ? dzu : 0.f;
-      acc[3 * MIP + 1] += isrow ? 0.f : dzu;
-      if (cok && live[u]) dpool[r * C + c] = g;
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < NA; ++e) red[(wave * 64 + lane) * NA + e] = acc[e];
-  __syncthreads();
-  if (blockIdx.x == 0 && blockIdx.y == 0 && tid < MIP) {
-    ly_gacc(dgamma, tid, ssum[MIP + tid], f64);
-    ly_gacc(dbeta, tid, ssum[tid], f64);
-  }
-  for (int e = tid; e < 64 * NA; e += LY_THREADS) {
-    const int cl = e / NA, k = e - cl * NA;
-    const int cc = blockIdx.x * 64 + cl;
-    if (cc >= C) continue;
-    const float v = red[e] + red[64 * NA + e] + red[2 * 64 * NA + e] + red[3 * 64 * NA + e];
-    if (k < MIP) ly_gacc(dw1, k * C + cc, v, f64);
-    else if (k < 2 * MIP) ly_gacc(dwh, cc * MIP + (k - MIP), v, f64);
-    else if (k < 3 * MIP) ly_gacc(dww, cc * MIP + (k - 2 * MIP), v, f64);
-    else if (k == 3 * MIP) ly_gacc(dbh, cc, v, f64);
-    else ly_gacc(dbw, cc, v, f64);
-  }
-}
-
-template <int MIP, int NS>
-static void launch_coordatt_bwd(hipStream_t st, const float* pool, int n_img, int H, int W, int C, const float* w1, const float* b1, const float* mean,
-                                const float* invstd, const float* gamma, const float* beta, const float* wh, const float* ww, const float* a_h,
-                                const float* a_w, const float* da_h, const float* da_w, float* ws, double* sums, float* dpool, float* dw1,
-                                float* dgamma, float* dbeta, float* dwh, float* dbh, float* dww, float* dbw, int f64) {
-  const long R = (long)n_img * (H + W);
-  long b1n = (R + 3) / 4;
-  if (b1n > 1024) b1n = 1024;
-  hipLaunchKernelGGL((ly_coordatt_mlp_bwd1_kernel<MIP, NS>), dim3((unsigned)b1n), dim3(LY_THREADS), 0, st, pool, n_img, H, W, C, w1, b1, mean, invstd, gamma,
-                     beta, wh, ww, a_h, a_w, da_h, da_w, ws, sums, dpool);
-  const int groups = (C + 63) / 64;
-  long chunks = (96 + groups - 1) / groups;                // ~96 blocks; each target address then receives `chunks` same-address adds
-  if (chunks > (R + 31) / 32) chunks = (R + 31) / 32;
-  if (chunks < 1) chunks = 1;
-  const long rpb = (R + chunks - 1) / chunks;
-  chunks = (R + rpb - 1) / rpb;
-  hipLaunchKernelGGL((ly_coordatt_mlp_bwd2_kernel<MIP>), dim3((unsigned)groups, (unsigned)chunks), dim3(LY_THREADS), 0, st, pool, n_img, H, W, C, rpb, w1,
-                     gamma, invstd, ws, sums, dpool, dw1, dgamma, dbeta, dwh, dbh, dww, dbw, f64);
-}
-
-extern "C" int ly_coordatt_mlp_bwd(const float* pool, int n_img, int H, int W, int C, int mip, const float* w1, const float* b1,
-                                   const float* mean, const float* invstd, const float* gamma, const float* beta, const float* wh,
-                                   const float* ww, const float* a_h, const float* a_w, const float* da_h, const float* da_w, float* ws,
-                                   double* sums, float* dpool, float* dw1, float* dgamma, float* dbeta, float* dwh, float* dbh,
-                                   float* dww, float* dbw, int grads_f64, void* stream) {
-  LY_CHECK(pool && w1 && b1 && mean && invstd && gamma && beta && wh && ww && a_h && a_w && da_h && da_w && ws && sums && dpool && dw1 &&
-               dgamma && dbeta && dwh && dbh && dww && dbw, "coordatt_mlp_bwd: null pointer");
-  LY_CHECK((mip == 8 || mip == 16) && C > 0 && C <= 512 && n_img > 0 && H > 0 && W > 0, "coordatt_mlp_bwd: built for mip 8 / 16 and C <= 512 (mip=%d C=%d)", mip, C);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define LY_CA_BWD(MIP, NS) launch_coordatt_bwd<MIP, NS>(st, pool, n_img, H, W, C, w1, b1, mean, invstd, gamma, beta, wh, ww, a_h, a_w, da_h, da_w, ws, sums, \
-                                                        dpool, dw1, dgamma, dbeta, dwh, dbh, dww, dbw, grads_f64)
-  const int ns = (C + 63) / 64;
-  if (mip == 8) {
-    if (ns <= 1) LY_CA_BWD(8, 1); else if (ns <= 2) LY_CA_BWD(8, 2); else if (ns <= 4) LY_CA_BWD(8, 4); else LY_CA_BWD(8, 8);
-  } else {
-    if (ns <= 4) LY_CA_BWD(16, 4); else LY_CA_BWD(16, 8);
-  }
-#undef LY_CA_BWD
-  LY_LAUNCH_CHECK();
-  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------

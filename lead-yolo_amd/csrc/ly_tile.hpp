@@ -85,6 +85,12 @@ template <> struct LyT<ly_f16img> {
   } while (0)
 #define LY_CHECK_DTYPE(dtype, who) LY_CHECK((dtype) == LY_F32 || (dtype) == LY_BF16, who ": unknown dtype %d", (dtype))
 
+// grid of the grid-stride elementwise kernels: four items per thread, at most 4096 blocks
+static inline long ly_ew_blocks(long items) {
+  long b = (items + LY_THREADS * 4L - 1) / (LY_THREADS * 4L);
+  return b < 1 ? 1 : b > 4096 ? 4096 : b;
+}
+
 __device__ __forceinline__ f32x4 ly_cvt4(const bf16x4 h) { return __builtin_convertvector(h, f32x4); }
 __device__ __forceinline__ bf16x4 ly_cvtb4(const f32x4 v) { return __builtin_convertvector(v, bf16x4); }
 

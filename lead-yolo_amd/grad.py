@@ -1,6 +1,7 @@
 """Training-step backward of the HIP path: torch.autograd.Function wrappers whose
 forward is the same HIP forward the inference path runs and whose backward is built from the HIP
-backward blocks in csrc/ly_backward.hip + the forward contraction kernels with transposed weights.
+backward blocks (csrc/ly_bnact.hip, ly_wgrad.hip, ly_backward.hip and each module's own file) + the forward
+contraction kernels with transposed weights.
 
 What autograd would derive for the reference's modules (train.py:324 `scaler.scale(loss).backward()`):
     Conv2d -> BatchNorm2d(train) -> SiLU/ReLU          models/common.py:1890-1910, 1537-1561
@@ -654,14 +655,12 @@ class MlpBlockFn(torch.autograd.Function):
                 dx, _ = ops.mlpblock_bwd_dx(g, dy, x, n, h, w, c, pack.packed(pack.src_taps(p_wpc, c4p, transposed_flipped=True), 9 * c4p, pl))
             elif ops.mlpblock_pconv(g, gz, n, h, w, c, pack.packed(pack.src_taps(p_wpc, c4p, transposed_flipped=True), 9 * c4p, pl)):
                 # gz = [t | g[c4:]] straight from the persistent kernel with the transposed-flipped taps: dx = dy + gz
-                _lib().check(_lib().lib().ly_mlp_dx(_lib().ptr(dy), _lib().ptr(gz), _lib().ptr(gz), c, m, c, 4, _lib().ptr(dx), _lib().dtype_code(dy),
-                                                    _lib().stream_ptr()), "ly_mlp_dx")
+                ops.mlp_dx(dy, gz, gz, c, m, c, 4, dx)
             else:
                 t = ops.empty_nhwc(n, c4p, h, w, x)
                 wt = pack.packed(pack.src_taps(p_wpc, c4q, transposed_flipped=True), 9 * c4q, pl)
                 ops.conv3x3(M=m, H=h, W=w, Cin=c4p, N=c4, x=g, ldx=c, wp=wt, out=t, ldo=c4p)
-                _lib().check(_lib().lib().ly_mlp_dx(_lib().ptr(dy), _lib().ptr(g), _lib().ptr(t), c4p, m, c, c4, _lib().ptr(dx), _lib().dtype_code(dy),
-                                                    _lib().stream_ptr()), "ly_mlp_dx")
+                ops.mlp_dx(dy, g, t, c4p, m, c, c4, dx)
             dwp, dw1, dw2 = gp.finish(), g1.finish(), g2.finish()
         return None, dx, dwp, dw1, dgamma, dbeta, dw2
 
@@ -713,7 +712,7 @@ MlpBlockFn._backward_fused = staticmethod(_mlpblock_backward_fused)
 class CoordAttFn(torch.autograd.Function):
     """The whole CoordAtt (models/common.py:1595-1609) as ONE autograd node: pools -> conv1 -> bn1 (batch statistics) -> h_swish ->
     conv_h / conv_w -> sigmoid -> gate.  Forward = the inference kernels plus the statistics pass (6 launches); backward = gate
-    backward, the two-launch MLP backward (csrc/ly_attention.hip, ly_coordatt_mlp_bwd) and the pool gradient added into dx in place.
+    backward, the two-launch MLP backward (csrc/ly_coordatt.hip, ly_coordatt_mlp_bwd) and the pool gradient added into dx in place.
     The same arithmetic as torch ops under autograd was ~60 launches of rocBLAS GEMMs on [n*(h+w), 8] matrices, native BatchNorm and
     elementwise kernels per block."""
 
@@ -793,28 +792,21 @@ class SppfPool(torch.autograd.Function):
                 ops.maxpool_bwd(buf, j * c, c4, acc, (j + 1) * c, c4, n, h, w, c, k, acc, j * c, c4)
             return acc[:, :c].to(buf.dtype), None
         # gather formulation (no atomics): the routing of all three pools in one launch, then level by level
-        L = _lib()
-        st = L.stream_ptr()
         dd = _rows_dense(d)
         if dd.dtype == buf.dtype:
-            # small maps (SPPF sits at stride 32): the three levels in ONE launch, map and routing in LDS (csrc/ly_backward.hip ly_sppf_bwd)
-            out = ops.empty_nhwc(n, c, h, w, buf)
-            rc = L.lib().ly_sppf_bwd(L.ptr(buf), c4, L.ptr(dd), c4, n, h, w, c, k, L.ptr(out), c, L.dtype_code(buf), st)
-            if rc == 0:
+            # small maps (SPPF sits at stride 32): the three levels in ONE launch, map and routing in LDS (csrc/ly_sppf.hip ly_sppf_bwd)
+            out = ops.sppf_bwd(buf, c4, dd, c4, n, h, w, c, k)
+            if out is not None:
                 return out, None
-            if rc != 1:
-                L.check(rc, "ly_sppf_bwd")
-        at = lambda t, off: ctypes.c_void_p(t.data_ptr() + t.element_size() * off)
         arg = torch.empty((n * h * w, 3 * c), dtype=torch.uint8, device=buf.device)
-        L.check(L.lib().ly_maxpool_arg(L.ptr(buf), c4, n, h, w, 3 * c, k, L.ptr(arg), 3 * c, L.dtype_code(buf), st), "ly_maxpool_arg")
+        ops.maxpool_arg(buf, c4, n, h, w, 3 * c, k, arg, 3 * c)
         up = dd[:, 3 * c:].float().contiguous(memory_format=torch.channels_last)            # total gradient of y3 = its direct gradient
         tmp = [torch.empty((n * h * w, c), dtype=torch.float32, device=buf.device) for _ in range(2)]
         out = ops.empty_nhwc(n, c, h, w, buf)
         up_p, up_ld = ops.rows(up)
         for j in (2, 1, 0):
             dst = out if j == 0 else tmp[j & 1]
-            L.check(L.lib().ly_maxpool_gather(at(arg, j * c), 3 * c, L.ptr(up_p) if j == 2 else L.ptr(tmp[(j + 1) & 1]), c, at(dd, j * c), c4, L.dtype_code(dd),
-                                              n, h, w, c, k, L.ptr(dst), c, L.dtype_code(dst), st), "ly_maxpool_gather")
+            ops.maxpool_gather(arg, j * c, 3 * c, up_p if j == 2 else tmp[(j + 1) & 1], c, dd, j * c, c4, n, h, w, c, k, dst, c)
         return out, None
 
 

@@ -1528,7 +1528,7 @@ def coordatt_gate_bwd(dout, x, ldx, n, h, w, c, a_h, a_w, ldd=None):
     """dout: rows of the incoming gradient with row stride ldd (default c: dense) — a channel slice of a wider gradient is read in place"""
     ldd = c if ldd is None else ldd
     dx = empty_nhwc(n, c, h, w, x)
-    # partial sums per column slab (da_h) / row band (da_w), plain stores, folded in index order: no atomics (csrc/ly_backward.hip)
+    # partial sums per column slab (da_h) / row band (da_w), plain stores, folded in index order: no atomics (csrc/ly_coordatt.hip)
     groups = 256 // (c // 4)
     slabs, bands = -(-w // (groups * 8)), -(-h // 8)
     ph = torch.empty((slabs, n * h * c), dtype=torch.float32, device=dout.device)
@@ -1555,6 +1555,35 @@ def maxpool_bwd(x, x_off, ldx, dy, dy_off, lddy, n, h, w, c, k, dx, dx_off, lddx
     assert dy.dtype == torch.float32 and dx.dtype == torch.float32
     capi.check(capi.lib().ly_maxpool_bwd(at(x, x_off), ldx, at(dy, dy_off), lddy, n, h, w, c, k, at(dx, dx_off), lddx, capi.dtype_code(x),
                                          capi.stream_ptr()), "ly_maxpool_bwd")
+
+
+def sppf_bwd(buf, ldb, d, ldd, n, h, w, c, k):
+    """the three chained pools' backward in ONE launch (csrc/ly_sppf.hip), map and routing in LDS: buf = the forward's [y | m(y) | m(m(y)) |
+    m(m(m(y)))] rows, d its gradient in the same dtype.  Returns dy, or None where the map does not fit (the entry's code 1)"""
+    out = empty_nhwc(n, c, h, w, buf)
+    rc = capi.lib().ly_sppf_bwd(_p(buf), ldb, _p(d), ldd, n, h, w, c, k, _p(out), c, capi.dtype_code(buf), capi.stream_ptr())
+    if rc == 0:
+        return out
+    if rc != 1:
+        capi.check(rc, "ly_sppf_bwd")
+    return None
+
+
+def maxpool_arg(x, ldx, n, h, w, c, k, arg, lda):
+    """arg (uint8 rows of lda): per window and channel the tap of its first maximum in row-major scan order, ATen's rule"""
+    capi.check(capi.lib().ly_maxpool_arg(_p(x), ldx, n, h, w, c, k, _p(arg), lda, capi.dtype_code(x), capi.stream_ptr()), "ly_maxpool_arg")
+
+
+def maxpool_gather(arg, arg_off, lda, d_up, ldu, d_own, own_off, ldd, n, h, w, c, k, out, ldo):
+    """out = d_own + the d_up (float32) of every window that routes to the position (arg: ly_maxpool_arg's); arg / d_own from a column offset"""
+    at = lambda t, off: ctypes.c_void_p(t.data_ptr() + t.element_size() * off)
+    capi.check(capi.lib().ly_maxpool_gather(at(arg, arg_off), lda, _p(d_up), ldu, at(d_own, own_off), ldd, capi.dtype_code(d_own), n, h, w, c, k,
+                                            _p(out), ldo, capi.dtype_code(out), capi.stream_ptr()), "ly_maxpool_gather")
+
+
+def mlp_dx(dy, g, t, ldt, rows, c, c4, dx):
+    """MLPBlock backward, last step: dx = dy + g, the first c4 channels dy + t (t rows of ldt)"""
+    capi.check(capi.lib().ly_mlp_dx(_p(dy), _p(g), _p(t), ldt, rows, c, c4, _p(dx), capi.dtype_code(dy), capi.stream_ptr()), "ly_mlp_dx")
 
 
 # ---- autoanchor (csrc/ly_anchors.hip; lead-yolo_amd/anchors.py holds the host loops) ------------------------------------------------

@@ -202,7 +202,7 @@ def rf3m_stream(gen_w, scale, shift, conv_w=None, mt=4, pool_stride=None):
 
 
 # --------------------------------------------------------------------------------------------------
-# Batched packing (csrc/ly_backward.hip ly_pack_table): every packed weight image of the model — forward, transposed for dgrad,
+# Batched packing (csrc/ly_pack.hip ly_pack_table): every packed weight image of the model — forward, transposed for dgrad,
 # tap-flipped, concatenated — is described ONCE by how it reads the fp32 parameter in place, and all of them are refreshed by a
 # single launch per optimisation step instead of 113-144 ly_frag_pack3 launches plus the permute / pad / cat temporaries feeding
 # them.  `packed(parts, K, planes)` returns the (persistent) packed tensor; it is refreshed lazily, when any source parameter

@@ -3,7 +3,7 @@
     ly_chan_moments -> ly_bn_finalize(_pair) -> ly_bnact_fwd
     ly_bnact_bwd_reduce(_pair) -> ly_bn_bwd_coeffs(_pair) -> ly_bnact_bwd_apply(_pair)          (+ ly_sum_rows)
 
-(csrc/ly_backward.hip, csrc/ly_attention.hip).  A plain helper module: tests/test_bnact_host.py (CPU) and tests/test_gpu_bnact.py (device)
+(csrc/ly_bnact.hip; ly_sum_rows in csrc/ly_backward.hip).  A plain helper module: tests/test_bnact_host.py (CPU) and tests/test_gpu_bnact.py (device)
 import the SAME references, judges, builders and case tables from here.
 
 References take the stored values — the fp32 / bf16 tensors a kernel is given — widened exactly to float64, and restate the operation in

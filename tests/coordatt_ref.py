@@ -3,7 +3,7 @@
     forward   ly_pool_hw -> ly_coordatt_conv1_stats -> (ly_bn_finalize) -> ly_coordatt_mlp -> ly_coordatt_gate
     backward  ly_coordatt_gate_bwd (+ ly_sum_rows) -> ly_coordatt_mlp_bwd (bwd1 + bwd2) -> ly_pool_hw_bwd (accumulating)
 
-(csrc/ly_attention.hip, csrc/ly_backward.hip; wired together by grad.CoordAttFn).  A plain helper module: tests/test_coordatt_host.py (CPU)
+(csrc/ly_coordatt.hip; ly_bn_finalize in csrc/ly_bnact.hip; wired together by grad.CoordAttFn).  A plain helper module: tests/test_coordatt_host.py (CPU)
 and tests/test_gpu_coordatt.py (device) import the SAME references, judges, builders and case tables from here.  The judges' forms and
 `_fail` are those of tests/bnact_ref.py and are imported from there.
 

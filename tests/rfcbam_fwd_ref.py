@@ -2,7 +2,7 @@
 
     k = 3, lane = channel       ly_rf3c_stats -> ly_rfcbam_mid -> ly_rf3c_fwd                        (csrc/ly_rf3c.hip, ly_rf3c.hpp)
     k = 3, matrix cores (bf16)  ly_rf3m_stats -> ly_rfcbam_mid -> ly_rf3m_fwd                        (csrc/ly_rf3m.hip)
-    k = 3, lane = pixel         ly_colsum, ly_rfcbam_stats (k = 3) -> ly_rfcbam_mid -> ly_rfcbam3_fwd   (csrc/ly_attention.hip, ly_rfcbam3.hip)
+    k = 3, lane = pixel         ly_colsum, ly_rfcbam_stats (k = 3) -> ly_rfcbam_mid -> ly_rfcbam3_fwd   (csrc/ly_rfcbam_att.hip, ly_rfcbam3.hip)
     k = 1                       ly_rfcbam_stats (k = 1) -> ly_rfcbam_mid -> ly_gemm_fwd with PRO_AFFINE_RELU_CA and rowscale
     the small steps             ly_colsum, ly_se_fwd, ly_rfcbam_mid, ly_rfa_map
 

@@ -4,7 +4,7 @@
                                                 -> (ly_bn_bwd_coeffs) -> ly_rf_bwd_gen -> ly_se_bwd -> ly_rf_bwd_dx
     k = 1    (grad._rfcbam_backward_k1)         ly_rf1_bwd 0 -> ly_rfa_bwd -> ly_rf1_bwd 1 -> (ly_bn_bwd_coeffs) -> ly_se_bwd -> ly_rf1_bwd 2
 
-(csrc/ly_rfcbam_bwd.hip, csrc/ly_rf1_bwd.hip, csrc/ly_attention.hip).  A plain helper module: tests/test_rfcbam_host.py (CPU) and
+(csrc/ly_rfcbam_bwd.hip, csrc/ly_rf1_bwd.hip, csrc/ly_rfcbam_att.hip).  A plain helper module: tests/test_rfcbam_host.py (CPU) and
 tests/test_gpu_rfcbam_bwd.py (device) import the SAME references, judges, builders and case tables from here.  The judges' forms, `_fail`,
 `nudge`, `in_band` and KINK are those of tests/bnact_ref.py and are imported from there.  Nothing here calls a kernel or lead_yolo_amd.ops.
 

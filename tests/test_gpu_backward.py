@@ -1202,7 +1202,7 @@ def test_large_lds_kernels_on_two_devices_of_one_process():
     """Kernels whose dynamic LDS exceeds the 64 KB a launch gets by default, launched on device 0 and then on device 1 from ONE process
     (skipped on a one-GPU box): the cap is a per-device function attribute (ly_launch_lds, csrc/ly_common.hpp), so the second device needs
     it set as well; a refused launch is the library's error return.  By the launchers' own formulas:
-      * ops.wgrad, plain-row 1x1, N = 128, Cin = 128, M = 2 * 16 * 16: the 128 x 128 tile of launch_wgrad_tiled (csrc/ly_backward.hip),
+      * ops.wgrad, plain-row 1x1, N = 128, Cin = 128, M = 2 * 16 * 16: the 128 x 128 tile of launch_wgrad_tiled (csrc/ly_wgrad.hip),
         one LDS buffer of PL * (PX / 8) rows of (128 + 128 + 16) * 16 B + 2 * 128 floats = 70,656 B for bf16 (PL 1, PX 128) and the same
         70,656 B for fp32 (PL 2, PX 64);
       * Conv k = 3, fp32, 128 -> 128 channels on 2 x 16 x 16 (ops.conv3x3, launch_conv3 in csrc/ly_conv3x3.hip): patch 16 x 8

@@ -4,7 +4,7 @@ Every contraction reads its weights from a packed image (pack.frag_pack3 and the
 pack.rfcbam_gen_weights_c, pack.rf3m_stream), never from the parameter.  The module tests see those images only through outputs at
 1e-3-class budgets: a zero lo plane, a dropped shift term or a descriptor that is right only at the model's shapes stays inside them.
 Here every element of every image is compared with a reference written as loops from the index maps stated in include/lead_yolo_hip.h,
-pack.py's docstrings, csrc/ly_tile.hpp and csrc/ly_attention.hip (ly_gw_index).  The references share no code with pack.py: bf16 rounding
+pack.py's docstrings, csrc/ly_tile.hpp and csrc/ly_rfcbam_att.hip (ly_gw_index).  The references share no code with pack.py: bf16 rounding
 is restated on the bits (round to nearest even), gathers are `for` loops, and no view / permute chain of pack.py is repeated.
 
 tests/test_gpu_pack.py holds the device kernels to these host packers; `emulate` (the LyPackDesc formula) is shared with it."""
@@ -141,7 +141,7 @@ def _gen_params(C, seed):
 
 
 def ref_gen_weights(gw, scale, shift, chunk, contiguous):
-    """element (ch, t, e) at (((((q*4 + w)*9 + t)*(per/2) + p)*10 + e)*2 + ab, with ly_gw_index's q, w, j, p, ab (csrc/ly_attention.hip)"""
+    """element (ch, t, e) at (((((q*4 + w)*9 + t)*(per/2) + p)*10 + e)*2 + ab, with ly_gw_index's q, w, j, p, ab (csrc/ly_rfcbam_att.hip)"""
     C = gw.shape[0] // 9
     cp = (C + chunk - 1) // chunk * chunk
     per = chunk // 4
